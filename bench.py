@@ -20,11 +20,17 @@ from the timed region's own plain and regularised iterations (`timed_region` car
 window holds no regularised iteration or no plain one, `value` falls back to the raw average and says so).
 
 Rank 0 prints ONE JSON line; besides the contract's keys it carries
+  losses          the last value of every logged loss (asserted finite)
+and, with --full only,
   roofline        the dominant hand-written kernel, timed per launch with HIP events inside the timed region
   cpu_baseline    the CPU oracle (oracle/) timed on this host on a bounded sample of the workload (64^2, batch 4, and one
                   iteration at the benchmark's own resolution for a same-resolution ratio)
   value_fp32_path the same iteration on the fp32-storage path (the path the 1e-3 parity gate is held on), batch 4
-  losses          the last value of every logged loss (asserted finite)
+  h2d, value_dead_work_elided, value_fp32_split_path, overlap.off_ms_per_step: the other legs below.
+A plain run (no --full) sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.
+
+--dump-outputs DIR writes what the timed path hands its caller after its last step (see dump_outputs) as .npy files; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -56,6 +62,12 @@ def parse_args():
                          "the G step); identical training trajectory, not used for the headline value")
     ap.add_argument("--ada", action="store_true",
                     help="wrap the discriminator in adaptive discriminator augmentation (BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel clock and roofline legs, "
+                         "the CPU oracle baseline, the fp32-storage and dead-work-elided legs, the host-to-device leg and "
+                         "(N > 1) the overlap-off leg; the --no-* options below drop single parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed into DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-clock", action="store_true")
     ap.add_argument("--clock-all", action="store_true",
@@ -73,7 +85,12 @@ def parse_args():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N ranks sharing cuda:0 over gloo (RCCL refuses two ranks on one device): rehearses the "
                          "launcher, the rendezvous and the exchange path on a 1-GPU box; not a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.clock_all or args.clock_only != "all") and not args.full:
+        ap.error("--clock-all / --clock-only shape the per-kernel clock, which runs with --full only")
+    return args
 
 
 def baseline_config(args, world) -> str:
@@ -247,6 +264,27 @@ def multi_rank_fields(world, backend, rehearsal, batch, steps, per_rank_seconds,
             if overlap_off_ms is not None else None}
 
 
+DUMP_SAMPLE = 1 << 22      # parameters dumped per model: 16 MiB of float32 each, 48 MiB for the three
+
+
+def dump_outputs(directory, trainer, last_losses):
+    """What a caller of the timed path receives after its last step: every loss that step logged (``<loss>.npy``, float64)
+    and the parameters of the generator, the discriminator and the EMA generator (``<model>_params.npy``, float32: the
+    model's parameters flattened in ``parameters()`` order; where a model has more than DUMP_SAMPLE of them, the elements
+    at DUMP_SAMPLE sorted indices drawn from a fixed seed, the same for every run of the same configuration)."""
+    import numpy
+    os.makedirs(directory, exist_ok=True)
+    for key, v in last_losses.items():
+        numpy.save(os.path.join(directory, f"{key}.npy"), numpy.asarray(v, dtype=numpy.float64))
+    for name, module in (("generator", trainer.generator), ("discriminator", trainer.discriminator),
+                         ("generator_ema", trainer.generator_ema)):
+        flat = torch.cat([p.detach().reshape(-1).float() for p in module.parameters()])
+        if flat.numel() > DUMP_SAMPLE:
+            pick = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[pick.to(flat.device)]
+        numpy.save(os.path.join(directory, f"{name}_params.npy"), flat.cpu().numpy())
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks of this script under torch.distributed.run (one
     process per GPU, RCCL rendezvous on 127.0.0.1) from a parent that never touches the GPU, relay their output
@@ -331,7 +369,7 @@ def main():
     trainer.pop_logs()
     clock_all = args.clock_all or bool(int(os.environ.get("MSG_CLOCK_SHAPES", "0")))
     roofline_keys = (("conv_fprop_row3", "conv_fprop_pp") if args.dtype == "bf16" else ("conv_fprop_dma",)) + ("upfirdn2d",)
-    _lib.kernel_clock.reset(enabled=not args.no_kernel_clock, only=None if clock_all else roofline_keys)
+    _lib.kernel_clock.reset(enabled=args.full and not args.no_kernel_clock, only=None if clock_all else roofline_keys)
     barrier()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     first_iteration = trainer.iteration + 1
@@ -342,6 +380,8 @@ def main():
         if args.clock_only != "all" and not args.no_kernel_clock:
             _lib.kernel_clock.enabled = ((first_iteration + k) % hp_lazy == 0) == (args.clock_only == "regularised")
         clock_iterations += int(_lib.kernel_clock.enabled)
+        if args.dump_outputs and k == args.steps - 1:
+            logged = {key: len(v) for key, v in trainer._log.items()}      # the log entries the last step appends
         trainer.train_iteration(batch_of())
         marks[k + 1].record()                                  # (one event per iteration: the plain / regularised split)
     barrier()
@@ -354,6 +394,11 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(split, op=torch.distributed.ReduceOp.MAX)     # the job is as slow as its slowest rank
     plain_ms, reg_ms = split.tolist()
+    logs = trainer.pop_logs()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, {key: v[logged.get(key, 0):] for key, v in logs.items()
+                                                  if len(v) > logged.get(key, 0)})
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     per_rank = [elapsed]
     overlap_off_ms = None
     if world > 1:
@@ -361,6 +406,7 @@ def main():
         torch.distributed.all_gather(every, torch.tensor([elapsed], device=dev, dtype=torch.float64))
         per_rank = [t.item() for t in every]
         elapsed = max(per_rank)                            # the job is as slow as its slowest rank
+    if world > 1 and args.full:
         # what the overlap buys: the same steps with every bucket exchanged after backward instead of during it
         # (outside the timed region of `value`)
         n_off = min(args.steps, 8)
@@ -378,7 +424,7 @@ def main():
     clock = _lib.kernel_clock.summary()
     _lib.kernel_clock.reset(enabled=False)
     h2d = None
-    if world == 1 and not args.no_h2d_leg and plain:
+    if world == 1 and args.full and not args.no_h2d_leg and plain:
         # the same plain iterations with the real batch arriving from PAGEABLE host memory every step through the data
         # feed (multi_stylegan_amd.data.DevicePrefetcher: pinned staging + copy stream, one iteration ahead) -- the only
         # host->device traffic of the reference's loop (model_wrapper.py:253-256).  Outside `value`'s timed region.
@@ -400,7 +446,8 @@ def main():
                "sample": f"{n_h2d} plain iterations, the real batch copied from pageable host memory every step through "
                          f"data.DevicePrefetcher (pinned double buffer, copy stream); amortised with the resident "
                          f"regularised iteration"}
-    logs = trainer.pop_logs()
+    for key, v in trainer.pop_logs().items():                 # (the --full legs' iterations log too)
+        logs.setdefault(key, []).extend(v)
     peak_mem = torch.cuda.max_memory_allocated(dev) / 2 ** 30
 
     if rank == 0:
@@ -412,7 +459,7 @@ def main():
         # achieved = algorithmic FLOPs of its launches inside the timed region / their HIP-event durations.
         pmc, pmc_file = {}, None       # HBM-side bytes per launch from separate rocprofv3 --pmc passes of this workload
         for name in sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_pmc_traffic.json")),
-                           reverse=True):
+                           reverse=True) if clock else ():
             try:
                 pmc = json.load(open(os.path.join(ROOT, "profiles", name)))["kernels"]
                 pmc_file = name
@@ -495,7 +542,7 @@ def main():
                         "variant": os.environ.get("MSG_LIB_VARIANT") or None,
                         "call_wrappers": "generated (_msg_fastcall)" if _lib.lib().fastcall else "ctypes"},
         }
-        if world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and not args.rehearse_on_one_gpu:
+        if args.full and world == 1 and not args.no_fp32_leg and args.dtype == "bf16" and not args.rehearse_on_one_gpu:
             del trainer, gen, dis, real
             torch.cuda.empty_cache()
             if not args.elide_dead_work:
@@ -507,7 +554,7 @@ def main():
             torch.cuda.empty_cache()
             note(f"fp32-storage legs with split-bf16 products (batch {args.batch}) ...")
             out["value_fp32_split_path"] = fp32_leg(args, dev, batch=args.batch, split="split_bf16x3")
-        if not args.no_cpu_baseline and world == 1:       # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:       # rank 0 at N=1 only
             note("CPU baseline (oracle, 64x64, B=4" + ("" if args.no_cpu_same_resolution else
                                                        f"; one iteration at {args.resolution}^2, B=2") + ") ...")
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_iters,

@@ -255,7 +255,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MSG_LIB_VARIANT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-fp32-leg"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-fp32-leg"]
     t0 = time.time()
     run = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     took = time.time() - t0

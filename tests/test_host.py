@@ -682,3 +682,33 @@ def test_bench_multi_rank_fields():
     assert one["rccl_ranks"] == 1 and one["backend"] is None and one["overlap"] is None
     reh = bench.multi_rank_fields(2, "gloo", True, 4, 3, [1.0, 1.0], 340.0)
     assert reh["backend"] == "gloo" and reh["rehearsal_shared_gpu"] is True
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's losses in float64, every model's parameters in float32 -- whole, or a seeded
+    sample of DUMP_SAMPLE of them that is the same in every run and holds the parameters' own values."""
+    import importlib.util
+    import types
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert 3 * bench.DUMP_SAMPLE * 4 <= 64 * 2 ** 20                      # the dump stays within 64 MB at any size
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 50)
+    torch.manual_seed(0)
+    big, small = torch.nn.Linear(8, 8), torch.nn.Linear(2, 3)            # 72 parameters (sampled) and 9 (whole)
+    trainer = types.SimpleNamespace(generator=big, discriminator=small, generator_ema=big)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), trainer, {"loss_generator": [0.25], "path_length": [1.5]})
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["discriminator_params.npy", "generator_ema_params.npy",
+                                                            "generator_params.npy", "loss_generator.npy", "path_length.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == (np.float64 if n.startswith(("loss", "path")) else np.float32) and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "path_length.npy").tolist() == [1.5]
+    whole = torch.cat([p.detach().reshape(-1) for p in small.parameters()]).numpy()
+    assert np.array_equal(np.load(tmp_path / "a" / "discriminator_params.npy"), whole)
+    sample = np.load(tmp_path / "a" / "generator_params.npy")
+    flat = torch.cat([p.detach().reshape(-1) for p in big.parameters()]).numpy()
+    assert sample.shape == (50,) and np.isin(sample, flat).all()

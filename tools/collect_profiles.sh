@@ -10,7 +10,7 @@ extra="$@"          # further bench.py arguments, e.g.  tools/collect_profiles.s
 out=gpurun_out/profiles_$tag
 mkdir -p $out
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
-legs="--no-cpu-baseline --no-fp32-leg --no-h2d-leg"      # the timed region only: the extra legs would add iterations to the trace
+legs="--full --no-cpu-baseline --no-fp32-leg --no-h2d-leg"      # the kernel clock, without the legs that would add iterations to the trace
 python bench.py $legs $extra > $out/bench_plain.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py $legs $extra > $out/bench_stats.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python bench.py --steps 2 --warmup 1 $legs --no-kernel-clock $extra > $out/bench_fetch.log 2>&1

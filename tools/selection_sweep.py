@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Reads the runs of tools/selection_sweep.sh (gpurun_out/sweep_*.json): for every (direction, shape) of the training step, the time
+"""Reads the runs of tools/selection_sweep.sh (python tools/selection_sweep.py OUT_DIR: OUT_DIR/sweep_*.json): for every (direction, shape) of the training step, the time
 per iteration under each forced kernel selection against the better of two default runs; lists what would be > 5 % faster."""
 import json
+import os
+import sys
 
 NAMES = ["variant1", "variant2", "pp0", "shortk0", "narrow0", "upconv0", "w32_0", "wgrow3_0", "wgw32_0", "lean0"]
 
 
 def load(name):
-    d = json.loads(open(f"gpurun_out/sweep_{name}.json").read().strip().splitlines()[-1])
+    d = json.loads(open(os.path.join(sys.argv[1], f"sweep_{name}.json")).read().strip().splitlines()[-1])
     steps = d.get("clock_iterations") or d["steps"]
     out = {}
     for k, v in d["kernels"].items():

@@ -1,8 +1,10 @@
 #!/bin/bash
 # Is the library's choice BETWEEN its kernels right, shape by shape?  The benchmark with per-shape clocks under every selection
 # tunable of a -DMSG_TUNING build (python -m multi_stylegan_amd.build --variant tuning --flags=-DMSG_TUNING), one process each;
-# tools/selection_sweep.py then compares every (direction, shape) against two default runs.  GPU box:  tools/selection_sweep.sh
-run() { name=$1; shift; env "$@" MSG_LIB_VARIANT=tuning MSG_CLOCK_SHAPES=1 python bench.py --no-cpu-baseline --no-fp32-leg --no-h2d-leg > gpurun_out/sweep_$name.json 2> gpurun_out/sweep_$name.err; echo "$name exit $?"; }
+# tools/selection_sweep.py then compares every (direction, shape) against two default runs.  GPU box:  tools/selection_sweep.sh OUT_DIR
+out=${1:?usage: tools/selection_sweep.sh OUT_DIR}
+mkdir -p "$out"
+run() { name=$1; shift; env "$@" MSG_LIB_VARIANT=tuning MSG_CLOCK_SHAPES=1 python bench.py --full --no-cpu-baseline --no-fp32-leg --no-h2d-leg > "$out/sweep_$name.json" 2> "$out/sweep_$name.err"; echo "$name exit $?"; }
 run s0 MSG_NOP=1
 run variant1 MSG_CONV_VARIANT=1          # generic forward kernel: LDS-DMA staging everywhere
 run variant2 MSG_CONV_VARIANT=2          # ... register staging everywhere

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-shape kernel-time table of the training step.
 
-    MSG_CLOCK_SHAPES=1 python bench.py --no-cpu-baseline > gpurun_out/bench_shapes.json
-    python tools/shape_table.py gpurun_out/bench_shapes.json
+    MSG_CLOCK_SHAPES=1 python bench.py --full --no-cpu-baseline > $OUT/bench_shapes.json
+    python tools/shape_table.py $OUT/bench_shapes.json
 
 Reads bench.py's JSON line (its "kernels" object, keyed per kernel and -- with MSG_CLOCK_SHAPES=1 -- per problem
 shape) and prints the entries sorted by total time per training iteration.

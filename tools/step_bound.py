@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """How far each launch of the training step is from max(compute, memory) -- a map of where the remaining time is.
 
-    MSG_CLOCK_SHAPES=1 python bench.py --no-cpu-baseline > gpurun_out/bench_shapes.json      (GPU box)
-    python tools/step_bound.py gpurun_out/bench_shapes.json [--mfma 1400] [--hbm 5000]
+    MSG_CLOCK_SHAPES=1 python bench.py --full --no-cpu-baseline > $OUT/bench_shapes.json      (GPU box)
+    python tools/step_bound.py $OUT/bench_shapes.json [--mfma 1400] [--hbm 5000]
 
 For every timed launch the floor is max(algorithmic FLOPs / R_mfma, algorithmic bytes / R_hbm) with R_mfma = what the dominant
 kernel SUSTAINS in this step (default 1 400 TFLOP/s: the clock the chip holds under bf16 MFMA streams) and
