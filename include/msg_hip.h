@@ -427,9 +427,9 @@ int msg_conv2d_fprop_act(const void* x, const void* w, void* y, int dtype,
                          const float* act_bias, const float* noise, const float* noise_weight,
                          int noise_batch, float alpha, float scale, void* stream);
 /* ... which also leaves the sign bytes of its output (see msg_upfirdn2d_separable_act_mask): mask, B * OH * OW * N / 8 bytes
- * in the order of the kernel's output tiles (256 pixels x 256 channels for plan 3, 128 x 128 for plan 4: the tile_m / tile_n of
- * msg_bias_act_backward_mask), or NULL.  Only the row-sharing 3x3 kernels write them (msg_conv2d_fprop_plan(...) == 3 or 4,
- * bf16): any other problem with mask != NULL is MSG_EUNSUPPORTED -- ask the plan first. */
+ * in the order of the kernel's output tiles (256 pixels x 256 channels for MSG_PLAN_ROW3, 128 x 128 for MSG_PLAN_ROW3N: the
+ * tile_m / tile_n of msg_bias_act_backward_mask), or NULL.  Only the row-sharing 3x3 kernels write them (msg_conv2d_fprop_plan(...)
+ * is MSG_PLAN_ROW3 or MSG_PLAN_ROW3N, bf16): any other problem with mask != NULL is MSG_EUNSUPPORTED -- ask the plan first. */
 int msg_conv2d_fprop_act_mask(const void* x, const void* w, void* y, int dtype,
                               int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                               int kh, int kw, int stride, int pad, long long w_batch_stride,
@@ -455,7 +455,8 @@ int msg_conv2d_fprop_residual(const void* x, const void* w, void* y, int dtype,
  * sign_ld) -- exactly one of the two.  residual: a second gradient of the same map (added first), or NULL.  noise [noise_batch]
  * [OH*OW] fp32 with grad_noise_weight, or both NULL.  Sums: fp32, overwritten, deterministic (per-tile partials in `ws`, summed in
  * index order; ws_floats >= msg_conv2d_fprop_act_backward_workspace(...)).  Only the row-sharing kernels have this epilogue:
- * MSG_EUNSUPPORTED unless msg_conv2d_fprop_plan(...) is 3 or 4 (the workspace query then returns 0), bf16, ldy == N. */
+ * MSG_EUNSUPPORTED unless msg_conv2d_fprop_plan(...) is MSG_PLAN_ROW3 or MSG_PLAN_ROW3N (the workspace query then returns 0),
+ * bf16, ldy == N. */
 long long msg_conv2d_fprop_act_backward_workspace(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW,
                                                   int N, int kh, int kw, long long w_batch_stride, int has_noise);
 int msg_conv2d_fprop_act_backward(const void* x, const void* w, void* y, int dtype,
@@ -511,9 +512,15 @@ int msg_linear_grouped_wgrad(const float* gy, const float* x, const int* slot, f
 int msg_linear_grouped_wgrad_ptrs(const float* gy, const float* x, const int* slot, float* const* gw, float* const* gb, int G,
                                   int M, int N, int K, int L, float gain, float bias_gain, void* stream);
 
-/* Which kernel msg_conv2d_fprop launches for a problem (no launch): 5 = the streaming kernels for 1x1 convolutions with
- * <= 8 channels on one side (conv_thin.hip), 3 / 4 = 3x3 row-sharing kernel with the 256x256 / 128x128 tile, 2 = 256x256
- * ping-pong, 1 = 128x128 with LDS-DMA staging, 0 = 128x128 with register staging.  Used by bench.py to label per-kernel timings. */
+/* Which kernel msg_conv2d_fprop launches for a problem (no launch).  Used by bench.py to label per-kernel timings. */
+enum {
+    MSG_PLAN_REG = 0,   /* 128x128 tile, register staging */
+    MSG_PLAN_DMA = 1,   /* 128x128 tile, LDS-DMA staging */
+    MSG_PLAN_PP = 2,    /* 256x256 ping-pong */
+    MSG_PLAN_ROW3 = 3,  /* 3x3 row-sharing kernel, 256x256 tile */
+    MSG_PLAN_ROW3N = 4, /* 3x3 row-sharing kernel, 128x128 tile */
+    MSG_PLAN_THIN = 5   /* the streaming kernels for 1x1 convolutions with <= 8 channels on one side (conv_thin.hip) */
+};
 int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
                           int kh, int kw, long long w_batch_stride);
 /* 1 if msg_conv2d_fprop takes this problem to the activation-stationary sub-pixel up-convolution kernel (conv_upconv.hip:

@@ -1,5 +1,9 @@
 """ctypes binding of libmsg_hip.so (C ABI: include/msg_hip.h).
 
+Nothing about that ABI is written down here: every entry point's signature, the status / storage / kernel-plan codes and
+the ABI version are parsed from the header at import (``_parse_header``), and the generated call wrappers
+(csrc_host/gen_fastcall.py) are built from the same parse.  A new entry point is declared in the header and nowhere else.
+
 There is no CPU fallback: if the shared library is missing or a call reports
 an error this raises.  Tensors are passed as raw device pointers together with
 the HIP stream torch is currently recording on, so launches interleave
@@ -18,84 +22,57 @@ LIB_PATH = os.path.join(_HERE, "libmsg_hip" + ("_" + os.environ["MSG_LIB_VARIANT
                         + ".so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "msg_hip.h")
 
-MSG_F32, MSG_BF16, MSG_F16, MSG_F64 = 0, 1, 2, 3
-ABI_VERSION = 5          # MSG_ABI_VERSION of include/msg_hip.h this binding was written against (checked at load time)
-_c = ctypes
-_P, _I, _L, _F = _c.c_void_p, _c.c_int, _c.c_longlong, _c.c_float
+_P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
+_BY_VALUE = {"int": _I, "long long": _L, "float": _F}
 
-_SIGNATURES = {
-    "msg_abi_version": (_I, []),
-    "msg_build_arch": (_c.c_char_p, []),
-    "msg_strerror": (_c.c_char_p, [_I]),
-    "msg_upfirdn2d": (_I, [_P, _P, _P, _I] + [_I] * 14 + [_P]),
-    "msg_upfirdn2d_pitched": (_I, [_P, _P, _P, _I] + [_I] * 15 + [_P]),
-    "msg_upfirdn2d_pitched2": (_I, [_P, _P, _P, _I] + [_I] * 16 + [_P]),
-    "msg_upfirdn2d_separable": (_I, [_P, _P, _P, _P, _I] + [_I] * 10 + [_P]),
-    "msg_upfirdn2d_separable_act": (_I, [_P, _P, _P, _P, _I] + [_I] * 10 + [_P, _P, _P, _I, _F, _F, _P]),
-    "msg_upfirdn2d_separable_act_mask": (_I, [_P, _P, _P, _P, _I] + [_I] * 10 + [_P, _P, _P, _I, _F, _F, _P, _P]),
-    "msg_fused_bias_act": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
-    "msg_bias_act_backward": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _I, _I, _F, _F, _P, _L, _P]),
-    "msg_channel_sums": (_I, [_P, _P, _I, _L, _I, _P, _L, _P]),
-    "msg_bias_act_backward_mask": (_I, [_P, _P, _I, _I, _P, _I, _L, _I, _P, _P, _P, _I, _I, _F, _F, _P, _L, _P]),
-    "msg_bias_act_backward_mask_head": (_I, [_P, _P, _P, _P, _F, _I, _P, _I, _I, _P, _I, _L, _I, _P, _P, _P, _I, _I, _F, _F,
-                                             _P, _L, _P]),
-    "msg_bias_act_backward_workspace": (_L, [_L, _I, _I, _I]),
-    "msg_conv2d_fprop": (_I, [_P, _P, _P, _P, _I] + [_I] * 15 + [_L, _P]),
-    "msg_conv2d_fprop_act": (_I, [_P, _P, _P, _I] + [_I] * 13 + [_L, _P, _P, _P, _I, _F, _F, _P]),
-    "msg_conv2d_fprop_act_mask": (_I, [_P, _P, _P, _I] + [_I] * 13 + [_L, _P, _P, _P, _I, _F, _F, _P, _P]),
-    "msg_conv2d_fprop_residual": (_I, [_P, _P, _P, _I] + [_I] * 13 + [_L, _P, _I, _F, _P]),
-    "msg_conv2d_fprop_act_backward_workspace": (_L, [_I] * 11 + [_L, _I]),
-    "msg_sum_rows": (_I, [_P, _P, _L, _I, _P]),
-    "msg_act_pointwise_head": (_I, [_P, _P, _P, _P, _I, _L, _I, _F, _F, _F, _P]),
-    "msg_act_pointwise_head_backward_workspace": (_L, [_L, _I]),
-    "msg_act_pointwise_head_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _F, _F, _P, _L, _P]),
-    "msg_conv2d_fprop_act_backward": (_I, [_P, _P, _P, _I] + [_I] * 13 + [_L, _P, _I, _P, _I, _I, _P, _I, _F, _F, _P, _P, _I, _P,
-                                           _P, _L, _P]),
-    "msg_conv2d_wgrad": (_I, [_P, _P, _P, _I] + [_I] * 18 + [_F, _P, _L, _P]),
-    "msg_conv2d_wgrad_workspace": (_L, [_I] * 18),
-    "msg_demod_coeff": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
-    "msg_scale_rows_cols": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
-    "msg_modulate_weights": (_I, [_P] * 5 + [_I] * 7 + [_F, _F, _P]),
-    "msg_modulate_backward": (_I, [_P] * 6 + [_I] * 6 + [_F, _P]),
-    "msg_modulate_backward2": (_I, [_P] * 7 + [_I] * 6 + [_F, _P]),
-    "msg_scale_rows_cols2": (_I, [_P] * 6 + [_I] * 6 + [_F, _P]),
-    "msg_relayout_weight": (_I, [_P, _P, _P, _P, _I] + [_I] * 7 + [_F, _P]),
-    "msg_gather_taps": (_I, [_P, _P, _I] + [_I] * 9 + [_P]),
-    "msg_fold_taps": (_I, [_P, _P, _P, _I] + [_I] * 10 + [_P]),
-    "msg_scaled_add": (_I, [_P, _P, _P, _I, _L, _F, _F, _P]),
-    "msg_rgb_skip_merge": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "msg_rgb_skip_merge_backward": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
-    "msg_gamma_merge": (_I, [_P, _P, _P, _P, _I, _L, _F, _P]),
-    "msg_gamma_merge_backward_workspace": (_L, []),
-    "msg_gamma_merge_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _F, _P, _P]),
-    "msg_scaled_add_rows": (_I, [_P, _P, _P, _I, _L, _I, _L, _L, _L, _F, _F, _P]),
-    "msg_flat_adam": (_I, [_P, _P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _I, _F, _P]),
-    "msg_flat_ema": (_I, [_P, _P, _L, _F, _P]),
-    "msg_softmax_rows": (_I, [_P, _P, _I, _L, _I, _P]),
-    "msg_softmax_rows_backward": (_I, [_P, _P, _P, _I, _L, _I, _P]),
-    "msg_softmax_rows_backward2": (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _P]),
-    "msg_nonlocal_attention_supported": (_I, [_I] * 5),
-    "msg_nonlocal_attention_fwd": (_I, [_P] * 5 + [_I] * 6 + [_P]),
-    "msg_nonlocal_attention_bwd_splits": (_I, [_I] * 3),
-    "msg_nonlocal_attention_bwd": (_I, [_P] * 14 + [_I] * 6 + [_P]),
-    "msg_affine_warp": (_I, [_P, _P, _P, _F, _P, _P, _P, _I, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "msg_minibatch_stddev_workspace": (_L, [_I] * 5),
-    "msg_minibatch_stddev": (_I, [_P, _P, _P, _P, _I] + [_I] * 7 + [_F, _P]),
-    "msg_minibatch_stddev_backward": (_I, [_P, _P, _P, _P, _I] + [_I] * 8 + [_F, _P]),
-    "msg_conv2d_fprop_plan": (_I, [_I] * 11 + [_L]),
-    "msg_conv2d_fprop_upconv_eligible": (_I, [_I] * 14 + [_L]),
-    "msg_conv2d_fprop_thin_eligible": (_I, [_I] * 16),
-    "msg_maxpool2x2_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _L, _P]),
-    "msg_maxpool2x2_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "msg_maxpool2x2_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _L, _P]),
-    "msg_linear_fprop": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
-    "msg_linear_dgrad": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
-    "msg_linear_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
-    "msg_linear_grouped_fprop": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
-    "msg_linear_grouped_dgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "msg_linear_grouped_wgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
-    "msg_linear_grouped_wgrad_ptrs": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
-}
+
+class MsgHipError(RuntimeError):
+    pass
+
+
+def _parse_header(text):
+    """The C ABI as include/msg_hip.h declares it -> ({entry point: (restype, [argtypes])}, {constant: int}): every
+    prototype ``RET msg_name(ARGS);``, every enumerator of the anonymous enums and ``#define MSG_ABI_VERSION n``.  The type
+    map is closed -- any pointer argument is a void*, a ``const char*`` result a char*, ``int`` / ``long long`` / ``float``
+    themselves -- and anything else raises, naming the entry: a type this binding cannot pass is never skipped or guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(MSG_\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    for body in re.findall(r"\benum\s*\{([^{}]*)\}", text):
+        for item in filter(str.strip, body.split(",")):
+            m = re.fullmatch(r"\s*(MSG_\w+)\s*=\s*(-?\d+)\s*", item)
+            if not m:
+                raise MsgHipError(f"{HEADER_PATH}: enumerator {item.strip()!r} is not `MSG_NAME = integer`")
+            consts[m[1]] = int(m[2])
+
+    def words(decl):
+        return " ".join(decl.replace("*", " * ").split())
+
+    sigs = {}
+    for ret, name, args in re.findall(r"\b([A-Za-z_][\w\s*]*?)\b(msg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        res = ctypes.c_char_p if words(ret) == "const char *" else _BY_VALUE.get(words(ret))
+        argtypes = []
+        for arg in ([] if words(args) == "void" else args.split(",")):
+            by_value = re.fullmatch(r"(int|long long|float) \w+", words(arg))
+            argtypes.append(_P if "*" in arg else by_value and _BY_VALUE[by_value[1]])
+        if res is None or None in argtypes or name in sigs:
+            raise MsgHipError(f"{HEADER_PATH}: `{words(ret)} {name}({words(args)})` has a type the binding cannot pass "
+                              "(arguments: pointers, int, long long, float, each with a name; results: int, long long, "
+                              "const char*) or is declared twice")
+        sigs[name] = (res, argtypes)
+    loose = re.findall(r"\b(msg_[a-z0-9_]+)\s*\(", text)
+    if len(loose) != len(sigs):
+        raise MsgHipError(f"{HEADER_PATH}: not a prototype this binding can read (`RET msg_name(ARGS);`, no nested "
+                          f"parentheses): {sorted(set(loose) - set(sigs)) or 'an entry declared twice'}")
+    return sigs, consts
+
+
+with open(HEADER_PATH) as _f:
+    _SIGNATURES, _CONSTANTS = _parse_header(_f.read())
+# the header's constants by their own names: MSG_OK / MSG_EINVAL / MSG_EUNSUPPORTED / MSG_ELAUNCH, the storage codes MSG_F32 /
+# MSG_BF16 / MSG_F16 / MSG_F64 / MSG_F32_SPLIT, the kernel plans MSG_PLAN_*, MSG_ABI_VERSION
+globals().update(_CONSTANTS)
+ABI_VERSION = _CONSTANTS["MSG_ABI_VERSION"]       # compared with the loaded library's msg_abi_version() in lib()
 
 
 def declared_symbols():
@@ -103,10 +80,6 @@ def declared_symbols():
     text = open(HEADER_PATH).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(msg_[a-z0-9_]+)\s*\(", text)))
-
-
-class MsgHipError(RuntimeError):
-    pass
 
 
 _lib = None

@@ -1,7 +1,8 @@
 """Build libmsg_hip.so (the C-ABI shared library of include/msg_hip.h) in-tree with hipcc for gfx950.
 
 ``python -m multi_stylegan_amd.build`` cross-compiles without a GPU.  The .so is git-ignored but travels to
-the GPU box with the repo snapshot.
+the GPU box with the repo snapshot.  include/msg_hip.h is the one place an entry point's shape is written: the library
+is compiled against it, and the Python binding (_lib.py) and the generated call wrappers (build_fastcall) are derived from it.
 """
 import glob
 import os
@@ -75,12 +76,13 @@ FASTCALL = os.path.join(HERE, "_msg_fastcall.so")
 
 
 def build_fastcall(force=False, verbose=True):
-    """The host-side call wrappers (csrc_host/gen_fastcall.py): C source generated from _lib._SIGNATURES, compiled with gcc
-    against this interpreter's headers into multi_stylegan_amd/_msg_fastcall.so.  One module serves the product library and
-    every variant build (it binds to whatever handle _lib loaded)."""
+    """The host-side call wrappers (csrc_host/gen_fastcall.py): C source generated from the prototypes of include/msg_hip.h (as
+    _lib parses them: _lib._SIGNATURES), compiled with gcc against this interpreter's headers into
+    multi_stylegan_amd/_msg_fastcall.so.  One module serves the product library and every variant build (it binds to whatever
+    handle _lib loaded)."""
     import sysconfig
     gen = os.path.join(HERE, "csrc_host", "gen_fastcall.py")
-    deps = [gen, os.path.join(HERE, "_lib.py")]
+    deps = [gen, os.path.join(HERE, "_lib.py"), os.path.join(HERE, "..", "include", "msg_hip.h")]
     if not force and os.path.exists(FASTCALL) and all(os.path.getmtime(FASTCALL) > os.path.getmtime(d) for d in deps):
         return FASTCALL
     sys.path.insert(0, os.path.dirname(HERE))

@@ -401,7 +401,7 @@ _CLOCK_SHAPES = bool(int(os.environ.get("MSG_CLOCK_SHAPES", "0")))   # per-shape
 #                     mantissa bits), fp32 accumulation: fp32-rounding-level error, held to the SAME step-trace tolerances
 #                     (tests/test_hip_models.py); bench.py reports it as its own leg.
 FP32_CONTRACTION = "exact"
-MSG_F32_SPLIT = 4
+MSG_F32_SPLIT = _lib.MSG_F32_SPLIT
 _SPLIT_CODES = {"split_bf16x3": MSG_F32_SPLIT}
 
 
@@ -437,6 +437,11 @@ def _contraction_code(t: torch.Tensor, mode: Optional[str] = None) -> int:
     return _SPLIT_CODES[mode] if (code == _lib.MSG_F32 and mode != "exact") else code
 
 
+# msg_conv2d_fprop_plan's kernel -> (its kernel-clock label, the output tile its activation epilogue leaves sign bytes in: only
+# the row-sharing 3x3 kernels write them)
+_PLANS = {_lib.MSG_PLAN_REG: ("conv_fprop_reg", None), _lib.MSG_PLAN_DMA: ("conv_fprop_dma", None),
+          _lib.MSG_PLAN_PP: ("conv_fprop_pp", None), _lib.MSG_PLAN_ROW3: ("conv_fprop_row3", 256),
+          _lib.MSG_PLAN_ROW3N: ("conv_fprop_row3n", 128), _lib.MSG_PLAN_THIN: ("conv_fprop_thin", None)}
 _PLAN_CACHE: dict = {}
 _WGRAD_WS_CACHE: dict = {}
 
@@ -476,10 +481,7 @@ def _launch_fprop(x, wk, ck, bias, n, out_hw, kh, kw, stride, pad, in_up, pixel_
     key = "conv_fprop"
     if _lib.kernel_clock.enabled:                       # label the timing with the kernel the library will pick
         plan = _lib.lib().msg_conv2d_fprop_plan(_lib.dtype_code(x), b, ih, iw, cx, ck, oh, ow, n, kh, kw, wstride)
-        key = ("conv_fprop_reg", "conv_fprop_dma", "conv_fprop_pp", "conv_fprop_row3", "conv_fprop_row3n",
-               "conv_fprop_thin")[plan]
-        if plan == 5 and act is not None:
-            key = "conv_fprop_reg"
+        key = _PLANS[_lib.MSG_PLAN_REG if plan == _lib.MSG_PLAN_THIN and act is not None else plan][0]
         if x.dtype == torch.bfloat16 and bias is None and act is None and residual is None and \
                 _lib.lib().msg_conv2d_fprop_upconv_eligible(b, ih, iw, cx, ck, oh, ow, n, kh, kw, stride, pad, in_up,
                                                            int(pixel_shuffle), wstride):
@@ -512,11 +514,12 @@ def _launch_fprop(x, wk, ck, bias, n, out_hw, kh, kw, stride, pad, in_up, pixel_
                 if mplan is None:          # (the library's kernel choice is a pure function of the geometry: asked once)
                     mplan = _PLAN_CACHE[pkey] = _lib.lib().msg_conv2d_fprop_plan(_lib.dtype_code(x), b, ih, iw, cx, ck, oh, ow,
                                                                                 n, kh, kw, wstride)
-                if mplan in (3, 4):
+                tile = _PLANS[mplan][1]
+                if tile:
                     from .op_static.fused_act import sign_mask_for
                     mask = sign_mask_for(b, n, oh, ow, x.dtype, dev)
                     if mask is not None:
-                        act[5].append((mask, 256 if mplan == 3 else 128, 256 if mplan == 3 else 128))
+                        act[5].append((mask, tile, tile))
             code = _lib.lib().msg_conv2d_fprop_act_mask(
                 xv.data_ptr(), wk.data_ptr(), y.data_ptr(), _contraction_code(x, mode), b, ih, iw, cx, ck, oh, ow, n, ldy, kh, kw,
                 stride, pad, wstride, _lib.ptr(act_bias), _lib.ptr(noise), _lib.ptr(noise_w),
@@ -785,8 +788,7 @@ def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle
     flops = 2.0 * b * h * w_ * n * kh * kw * c_real
     key = "conv_fprop_row3_actbwd"
     if _lib.kernel_clock.enabled:                       # (the 256 x 256 tile -- the benchmark's roofline kernel -- or the 128 x 128 one)
-        if _lib.lib().msg_conv2d_fprop_plan(_lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, kh, kw, wstride) == 4:
-            key = "conv_fprop_row3n_actbwd"
+        key = _PLANS[_lib.lib().msg_conv2d_fprop_plan(_lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, kh, kw, wstride)][0] + "_actbwd"
     if _lib.kernel_clock.enabled and _CLOCK_SHAPES:
         key += f"|B{b} {h}x{w_}->{h}x{w_} {c_real}->{n} 3x3 s1 up1{' per-sample' if per_sample else ''}|"
     with _lib.on_device(dev), _lib.kernel_clock.span((key, 'bf16'), flops):
@@ -794,7 +796,7 @@ def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle
             xv.data_ptr(), wk.data_ptr(), y.data_ptr(), _lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, ldy, kh, kw, 1, 1, wstride,
             _lib.ptr(rv), res_ld, _lib.ptr(smask), tm, tn, _lib.ptr(smap), sld, handle.alpha, handle.scale,
             _lib.ptr(gb), _lib.ptr(nz), nb, _lib.ptr(gnw), ws, need, _lib.stream_of(dev))
-    if code == -2:
+    if code == _lib.MSG_EUNSUPPORTED:
         _ACTBWD_WS_CACHE[wkey] = 0          # (not asked again for this geometry)
         return None
     _lib.check(code, "msg_conv2d_fprop_act_backward")

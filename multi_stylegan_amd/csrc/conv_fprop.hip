@@ -518,26 +518,27 @@ extern "C" int msg_conv2d_fprop_thin_eligible(int B, int IH, int IW, int Cx, int
                                               int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
                                               int act_mode);
 
-// Which kernel msg_conv2d_fprop would launch for this problem: 5 = the streaming kernels of conv_thin.hip (1x1, <= 8 channels on
-// one side; assuming no fused activation), 3 / 4 = conv_fprop_row3_kernel<4,4> / <2,2> (3x3 'same' convs
-// on wide maps, activation tile shared by the horizontal taps; 256x256 / 128x128 tile), 2 = conv_fprop_pp_kernel (256x256 ping-pong),
-// 1 = conv_fprop_kernel<T, true> (128x128, LDS-DMA staging), 0 = conv_fprop_kernel<T, false> (register staging).
+// Which kernel msg_conv2d_fprop would launch for this problem (the MSG_PLAN_* codes of msg_hip.h): THIN = the streaming kernels of
+// conv_thin.hip (1x1, <= 8 channels on one side; assuming no fused activation), ROW3 / ROW3N = conv_fprop_row3_kernel<4,4> / <2,2>
+// (3x3 'same' convs on wide maps, activation tile shared by the horizontal taps; 256x256 / 128x128 tile), PP = conv_fprop_pp_kernel
+// (256x256 ping-pong), DMA = conv_fprop_kernel<T, true> (128x128, LDS-DMA staging), REG = conv_fprop_kernel<T, false> (register
+// staging).
 extern "C" int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
                                      int kh, int kw, long long w_batch_stride) {
     if (dtype == MSG_BF16 && msg_conv2d_fprop_thin_eligible(B, IH, IW, Cx, Ck, OH, OW, N, N <= 8 ? 8 : (N + 7) / 8 * 8, kh, kw, 1,
                                                             0, 1, 0, 0))
-        return 5;
+        return MSG_PLAN_THIN;
     if (dtype == MSG_BF16) {
         const int r3 = msg_conv2d_fprop_row3_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
-        if (r3) return r3 == 1 ? 3 : 4;
+        if (r3) return r3 == 1 ? MSG_PLAN_ROW3 : MSG_PLAN_ROW3N;
     }
-    if (dtype == MSG_BF16 && msg_conv2d_fprop_pp_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride)) return 2;
+    if (dtype == MSG_BF16 && msg_conv2d_fprop_pp_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride)) return MSG_PLAN_PP;
     const int esz = dtype == MSG_BF16 ? 2 : 4;
     const int n_iters = kh * kw * (Ck / (128 / esz));
     static const int variant = msg_tunable("MSG_CONV_VARIANT", 0);
     const bool fits31 = (long long)(w_batch_stride ? 1 : B) * IH * IW * Cx * esz < 0x7ffffff0ll &&
                         (long long)N * kh * kw * Ck * esz < 0x7ffffff0ll;
-    return (fits31 && (variant == 1 || (variant == 0 && n_iters >= 8))) ? 1 : 0;
+    return (fits31 && (variant == 1 || (variant == 0 && n_iters >= 8))) ? MSG_PLAN_DMA : MSG_PLAN_REG;
 }
 
 static int conv2d_fprop_impl(const void* x, const void* w, const float* bias, void* y, int dtype,
@@ -563,7 +564,8 @@ extern "C" int msg_conv2d_fprop_act_mask(const void* x, const void* w, void* y, 
     if (mask) {
         // only the row-sharing 3x3 kernel writes the sign bytes: the caller asks msg_conv2d_fprop_plan first
         const int plan = msg_conv2d_fprop_plan(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
-        if (dtype != MSG_BF16 || N % 8 || stride != 1 || pad != 1 || (plan != 3 && plan != 4)) return MSG_EUNSUPPORTED;
+        if (dtype != MSG_BF16 || N % 8 || stride != 1 || pad != 1 || (plan != MSG_PLAN_ROW3 && plan != MSG_PLAN_ROW3N))
+            return MSG_EUNSUPPORTED;
     }
     ActEpilogue act{act_bias, noise, noise_weight, noise_batch, 1, alpha, scale, nullptr, 0, 0.f, mask};
     return conv2d_fprop_impl(x, w, nullptr, y, dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0,
@@ -600,8 +602,8 @@ static void act_backward_partials(int dtype, int B, int IH, int IW, int Cx, int 
                                   long long w_batch_stride, long long* rows, long long* entries) {
     *rows = *entries = 0;
     const int plan = msg_conv2d_fprop_plan(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
-    if (dtype != MSG_BF16 || (plan != 3 && plan != 4)) return;
-    const int hm = plan == 3 ? 256 : 128;
+    if (dtype != MSG_BF16 || (plan != MSG_PLAN_ROW3 && plan != MSG_PLAN_ROW3N)) return;
+    const int hm = plan == MSG_PLAN_ROW3 ? 256 : 128;
     const long long mtot = w_batch_stride ? (long long)OH * OW : (long long)B * OH * OW;
     const long long tiles = (mtot / hm) * (w_batch_stride ? B : 1);
     *rows = tiles * 2;
@@ -620,7 +622,7 @@ extern "C" long long msg_conv2d_fprop_act_backward_workspace(int dtype, int B, i
 // and the stage's bias / noise-weight gradients -- the map between the two backward nodes is never written.  s: `sign_mask`
 // (bytes of msg_conv2d_fprop_act_mask / msg_upfirdn2d_separable_act_mask in tiles mask_tile_m x mask_tile_n; tile_m 1 or a
 // multiple of 64) or `sign_map` (the stage's stored output, bf16, channel pitch sign_ld).  Only the row-sharing kernels
-// (msg_conv2d_fprop_plan == 3 or 4) have this epilogue: MSG_EUNSUPPORTED otherwise, as for anything but bf16.
+// (msg_conv2d_fprop_plan: MSG_PLAN_ROW3 / MSG_PLAN_ROW3N) have this epilogue: MSG_EUNSUPPORTED otherwise, as for anything but bf16.
 extern "C" int msg_conv2d_fprop_act_backward(const void* x, const void* w, void* y, int dtype,
                                              int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                                              int kh, int kw, int stride, int pad, long long w_batch_stride,

@@ -126,7 +126,7 @@ def act_backward_with_head(gy, head, out_shape, noise, bias_param, need_bias, ne
             mbytes.data_ptr(), int(tile_m), int(tile_n), gx.data_ptr(), _lib.MSG_BF16, gx.numel(), c,
             _lib.ptr(gb), _lib.ptr(nz), _lib.ptr(gnw), nb, h * w, float(negative_slope), float(scale),
             ws, need, _lib.stream_of(dev))
-    if code == -2:                      # MSG_EUNSUPPORTED (shapes whose workgroups would straddle samples, alignment)
+    if code == _lib.MSG_EUNSUPPORTED:   # (shapes whose workgroups would straddle samples, alignment)
         return None
     _lib.check(code, "msg_bias_act_backward_mask_head")
     return gx, (gb if gb is not None else torch.zeros(0, device=dev)), (gnw if gnw is not None else torch.zeros(0, device=dev))
@@ -184,7 +184,7 @@ class FusedLeakyReLUFunctionBackward(Function):
                     g.numel(), channels,
                     _lib.ptr(gb), _lib.ptr(nz), _lib.ptr(gnw), nb, pix, float(negative_slope), float(scale),
                     ws, need, _lib.stream_of(dev))
-            if code == -2:                          # MSG_EUNSUPPORTED: the backward's vector path has stricter conditions
+            if code == _lib.MSG_EUNSUPPORTED:       # the backward's vector path has stricter conditions
                 mask = None                         # (pointer alignment) than the forward's decision to write the bytes --
             else:                                   # the stored output is still here, take the slower path instead of raising
                 _lib.check(code, "msg_bias_act_backward_mask")
@@ -232,7 +232,7 @@ class FusedLeakyReLUFunctionBackward(Function):
                     g.data_ptr(), mbytes.data_ptr(), int(tile_m), int(tile_n), gx.data_ptr(), _lib.MSG_BF16, g.numel(),
                     g.shape[1], None, None, None, 1, g.shape[2] * g.shape[3], float(negative_slope), float(scale), None, 0,
                     _lib.stream_of(dev))
-            if code != -2:
+            if code != _lib.MSG_EUNSUPPORTED:
                 _lib.check(code, "msg_bias_act_backward_mask")
                 return gx, None, None, None, None, None, None
         gg_out = _bias_act(gg_input, ggb, out, noise if ggw is not None else None, ggw, 1, negative_slope, scale)

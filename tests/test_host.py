@@ -3,6 +3,7 @@ gradient-bucket reducer and the trainer's data-parallel path under gloo (world s
 import ctypes
 import json
 import os
+import re
 import sys
 
 import pytest
@@ -23,7 +24,76 @@ def test_library_exports_every_declared_symbol():
     for name in names:
         assert hasattr(handle, name), f"{name} declared in include/msg_hip.h but not exported"
     assert _lib.lib().msg_build_arch() == b"gfx950" and _lib.lib().msg_abi_version() >= 1
-    assert set(_lib._SIGNATURES) == set(names)            # the ctypes table binds all of them, nothing else
+    # the binding is parsed from the header by a strict reader: it saw every name this loose regex sees, nothing else
+    assert set(_lib._SIGNATURES) == set(names) and len(names) >= 69
+
+
+def _stripped_header():
+    from multi_stylegan_amd import _lib
+    with open(_lib.HEADER_PATH) as f:
+        return re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+
+
+def test_binding_types_are_the_headers():
+    """Pins on the header-derived signatures and constants that do not go through the parser's own output: written here from
+    reading include/msg_hip.h.  A shifted or narrowed argument reaches the kernels as a wrong stride or pointer."""
+    from multi_stylegan_amd import _lib, conv_ops
+    from multi_stylegan_amd.build import build
+    build(verbose=False)
+    c, sig = ctypes, _lib._SIGNATURES
+    P, I, L, F = c.c_void_p, c.c_int, c.c_longlong, c.c_float
+    assert sig["msg_strerror"] == (c.c_char_p, [I]) and sig["msg_build_arch"] == (c.c_char_p, [])
+    assert sig["msg_abi_version"] == (I, [])
+    sizes = [n for n in sig if n.endswith("_workspace")]
+    assert len(sizes) >= 6 and all(sig[n][0] is L for n in sizes)
+    assert all(res is I for n, (res, _a) in sig.items() if n not in sizes and n not in ("msg_strerror", "msg_build_arch"))
+    res, args = sig["msg_conv2d_fprop"]
+    assert res is I and len(args) == 22 and args[:5] == [P, P, P, P, I] and args[5:20] == [I] * 15
+    assert args[20] is L and args[21] is P                                   # w_batch_stride, stream
+    assert sig["msg_conv2d_fprop_plan"] == (I, [I] * 11 + [L])
+    assert sig["msg_flat_adam"] == (I, [P, P, P, P, P, L, P, F, F, F, F, I, F, P])
+    assert sig["msg_flat_ema"] == (I, [P, P, L, F, P])
+    assert sig["msg_bias_act_backward_workspace"] == (L, [L, I, I, I])
+    assert sig["msg_gamma_merge_backward_workspace"] == (L, [])
+    assert (_lib.MSG_OK, _lib.MSG_EINVAL, _lib.MSG_EUNSUPPORTED, _lib.MSG_ELAUNCH) == (0, -1, -2, -3)
+    assert (_lib.MSG_F32, _lib.MSG_BF16, _lib.MSG_F16, _lib.MSG_F64, _lib.MSG_F32_SPLIT) == (0, 1, 2, 3, 4)
+    assert conv_ops.MSG_F32_SPLIT == 4
+    assert (_lib.MSG_PLAN_REG, _lib.MSG_PLAN_DMA, _lib.MSG_PLAN_PP, _lib.MSG_PLAN_ROW3, _lib.MSG_PLAN_ROW3N,
+            _lib.MSG_PLAN_THIN) == (0, 1, 2, 3, 4, 5)
+    # the kernel-clock labels bench.py, profiles/ and the tools key on, and the tile of the sign bytes, per plan
+    assert conv_ops._PLANS == {0: ("conv_fprop_reg", None), 1: ("conv_fprop_dma", None), 2: ("conv_fprop_pp", None),
+                               3: ("conv_fprop_row3", 256), 4: ("conv_fprop_row3n", 128), 5: ("conv_fprop_thin", None)}
+    assert _lib.ABI_VERSION == _lib.lib().msg_abi_version() == 5
+    assert _lib.lib().msg_strerror(_lib.MSG_EUNSUPPORTED) != _lib.lib().msg_strerror(_lib.MSG_EINVAL)
+    # every `msg_name(` of the comment-stripped header became exactly one parsed prototype
+    assert len(re.findall(r"\bmsg_[a-z0-9_]+\s*\(", _stripped_header())) == len(sig)
+
+
+_REFUSED = {
+    "msg_new_double": "int msg_new_double(const float* x, double gain, void* stream);",
+    "msg_new_struct": "typedef struct { int b, h, w; } msg_shape;\nint msg_new_struct(const void* x, msg_shape shape, void* stream);",
+    "msg_new_callback": "int msg_new_callback(const void* x, void (*done)(int), void* stream);",   # (read up to `(*done)`: truncated)
+    "msg_new_unnamed": "int msg_new_unnamed(const void*, int, void*);",
+    "msg_new_result": "double msg_new_result(const void* x);",
+    "msg_strerror": "const char* msg_strerror(int code);",                                         # (declared twice)
+}
+
+
+@pytest.mark.parametrize("name", sorted(_REFUSED))
+def test_binding_refuses_what_it_cannot_pass(name):
+    """A prototype with a type outside the closed map (pointers, int, long long, float), one the reader would truncate, or a
+    second declaration: the import-time parse raises and names the entry -- nothing is skipped or guessed."""
+    from multi_stylegan_amd import _lib
+    with open(_lib.HEADER_PATH) as f:
+        text = f.read()
+    mark = "#ifdef __cplusplus\n}"
+    assert text.count(mark) == 1
+    assert len(_lib._parse_header(text)[0]) == len(_lib._SIGNATURES)
+    with pytest.raises(_lib.MsgHipError, match=name):
+        _lib._parse_header(text.replace(mark, _REFUSED[name] + "\n" + mark))
+    ok = text.replace(mark, "long long msg_new_fine(const unsigned char* const* x, long long n,\n float g, void* stream);\n" + mark)
+    assert _lib._parse_header(ok)[0]["msg_new_fine"] == (ctypes.c_longlong, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float,
+                                                                            ctypes.c_void_p])
 
 
 def test_product_modules_keep_reference_surface():
@@ -331,13 +401,13 @@ def test_kernel_plans_respect_the_31_bit_offset_limits():
     bf16 = _lib.MSG_BF16
     plan = lambda b, c, n, hw, k, ws: lib.msg_conv2d_fprop_plan(bf16, b, hw, hw, c, c, hw, hw, n, k, k, ws)
     # 3x3 512 -> 512 @256^2: per-sample weights (one sample per descriptor) and a shared-weight batch of 0.5 GiB: the 256 x 256 tile
-    assert plan(16, 512, 512, 256, 3, 512 * 512 * 9) == 3
-    assert plan(8, 512, 512, 256, 3, 0) == 3
+    assert plan(16, 512, 512, 256, 3, 512 * 512 * 9) == _lib.MSG_PLAN_ROW3 == 3
+    assert plan(8, 512, 512, 256, 3, 0) == _lib.MSG_PLAN_ROW3
     # the same layer over 33 samples with SHARED weights: 2.2 GiB behind one descriptor -> register-staged 128 x 128 kernel
-    assert plan(33, 512, 512, 256, 3, 0) == 0
-    # 1x1 512 -> 256 (ping-pong kernel's territory: plan 2) likewise
-    assert plan(16, 512, 256, 256, 1, 0) == 2
-    assert plan(33, 512, 256, 256, 1, 0) == 0
+    assert plan(33, 512, 512, 256, 3, 0) == _lib.MSG_PLAN_REG == 0
+    # 1x1 512 -> 256 (ping-pong kernel's territory: MSG_PLAN_PP) likewise
+    assert plan(16, 512, 256, 256, 1, 0) == _lib.MSG_PLAN_PP == 2
+    assert plan(33, 512, 256, 256, 1, 0) == _lib.MSG_PLAN_REG
     # weight-gradient workspace queries (plan only) on the discriminator's stride-2 outputs: 127, 63, 31, 15 wide
     for c, ihw, ohw in ((128, 256, 127), (256, 128, 63), (384, 64, 31), (768, 32, 15)):
         need = lib.msg_conv2d_wgrad_workspace(bf16, 32, ihw, ihw, c, c, ohw, ohw, c, c, c, 3, 3, 2, 0, 0, 0, 1)
