@@ -1,0 +1,102 @@
+// Host-side dispatch of the convolution family (internal; included by the conv_*.hip files): the description of a problem,
+// the answer to "which kernel runs it", and the prototype of every function one file of the family calls in another --
+// declared here once, and seen by the definitions too, so that the compiler checks them (msg_bias_act_reduce_launch, which files
+// outside the family call as well, is in msg_common.h).
+//
+// Forward convolutions and data gradients (msg_conv2d_fprop*): conv_fprop_select (conv_fprop.hip) is the only place that knows the
+// order thin, upconv, row3, pp, generic.  Each kernel file gives it `bool conv_<k>_eligible(problem, ..., ConvPlan*)` holding ALL of
+// that kernel's conditions (it fills the plan when it says yes) and `void conv_<k>_launch(problem, plan, pointers, stream)`, which
+// cannot decline.  Everything that asks "what would run" -- msg_conv2d_fprop_plan, the sign-byte gate, the activation-backward
+// workspace -- asks conv_fprop_select, i.e. the code the launch goes through.
+// Weight gradients (msg_conv2d_wgrad*): wgrad_impl / conv_wgrad_row3_try plan and launch through the same code (plan_only).
+#pragma once
+#include "msg_common.h"
+
+struct ConvProblem {
+    int dtype;                      // MSG_F32 or MSG_BF16 (MSG_F32_SPLIT arrives here as MSG_F32 with split = 3)
+    int split;
+    int B, IH, IW, Cx, Ck, OH, OW, N, ldy;
+    int kh, kw, stride, pad, in_up, pixel_shuffle;
+    long long w_batch_stride;       // elements between the weight sets of two samples; 0: one set for the batch
+
+    bool per_sample() const { return w_batch_stride != 0; }
+    int samples() const { return per_sample() ? B : 1; }                                   // grid.z of the tile kernels
+    long long mtot() const { return per_sample() ? (long long)OH * OW : (long long)B * OH * OW; }   // GEMM rows of one grid.z slice
+    int esz() const { return dtype == MSG_BF16 ? 2 : 4; }
+    long long x_bstride() const { return (long long)IH * IW * Cx; }                        // elements per sample
+    long long y_bstride() const { return (pixel_shuffle ? 4ll : 1ll) * OH * OW * ldy; }
+    // what one buffer descriptor spans: the activations of the batch (of one sample with per-sample weights), one weight set
+    long long x_bytes() const { return (long long)(per_sample() ? 1 : B) * IH * IW * Cx * esz(); }
+    long long w_bytes() const { return (long long)N * kh * kw * Ck * esz(); }
+    // the kernels that address through descriptors use 31-bit offsets (num_records 2^31 - 16, msg_make_desc)
+    bool fits31() const { return x_bytes() < 0x7ffffff0ll && w_bytes() < 0x7ffffff0ll; }
+};
+
+enum ConvKernel {
+    CONV_THIN_N, CONV_THIN_K,       // conv_thin.hip: streaming 1x1 kernels, <= 8 output / 8 input channels
+    CONV_UPCONV,                    // conv_upconv.hip: activation-stationary sub-pixel up-convolution
+    CONV_ROW3, CONV_ROW3N,          // conv_fprop_row3.hip: row-sharing 3x3, 256 x 256 / 128 x 128 tile
+    CONV_PP,                        // conv_fprop_pp.hip: 256 x 256 ping-pong
+    CONV_DMA, CONV_REG, CONV_REG_LEAN, CONV_REG_SPLIT   // conv_fprop.hip: 128 x 128 tile; LDS-DMA / register staging (+ lean, split-bf16)
+};
+
+struct ConvPlan {
+    ConvKernel kernel;
+    int tile_m, tile_n;             // output tile of the MFMA kernels (pixels x channels); 0 for the streaming kernels
+    bool supported;                 // false: no kernel takes the problem (the generic kernel's own limits): MSG_EUNSUPPORTED
+};
+
+inline int conv_act_mode(const ActEpilogue* act) { return act ? act->enabled : 0; }
+
+// The fields the tile kernels' parameter structs (ConvParams, ConvParamsPP, ConvParamsR3) share under one name.
+template <typename P>
+inline void conv_fill_common(P& p, const ConvProblem& q, const ActEpilogue* act) {
+    p.B = q.B; p.IH = q.IH; p.IW = q.IW; p.Cx = q.Cx; p.Ck = q.Ck; p.OH = q.OH; p.OW = q.OW; p.N = q.N; p.ldy = q.ldy;
+    p.per_sample = q.per_sample();
+    if (act) p.act = *act;
+    p.x_bstride = q.x_bstride();
+    p.w_bstride = q.w_batch_stride;
+    p.y_bstride = q.y_bstride();
+    p.Mtot = (int)q.mtot();
+}
+// ... and the tap geometry of the two that take any (ConvParams, ConvParamsPP)
+template <typename P>
+inline void conv_fill_taps(P& p, const ConvProblem& q) {
+    p.kh = q.kh; p.kw = q.kw; p.stride = q.stride; p.pad = q.pad; p.in_up = q.in_up; p.pixel_shuffle = q.pixel_shuffle;
+}
+
+ConvPlan conv_fprop_select(const ConvProblem& q, const ActEpilogue* act, bool has_bias);
+
+// conv_thin.hip
+bool conv_thin_eligible(const ConvProblem& q, const ActEpilogue* act, ConvPlan* plan);
+void conv_thin_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, const float* bias, void* y,
+                      const ActEpilogue* act, void* stream);
+// conv_upconv.hip
+bool conv_upconv_eligible(const ConvProblem& q, const ActEpilogue* act, bool has_bias, ConvPlan* plan);
+void conv_upconv_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, void* y, void* stream);
+// conv_fprop_row3.hip
+bool conv_row3_eligible(const ConvProblem& q, const ActEpilogue* act, bool has_bias, ConvPlan* plan);
+void conv_row3_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, const float* bias, void* y,
+                      const ActEpilogue* act, void* stream);
+// conv_fprop_pp.hip
+bool conv_pp_eligible(const ConvProblem& q, ConvPlan* plan);
+void conv_pp_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, const float* bias, void* y,
+                    const ActEpilogue* act, void* stream);
+
+// ---- weight gradients
+struct WgradProblem {
+    int dtype;                      // MSG_F32 or MSG_BF16 (MSG_F32_SPLIT: MSG_F32 with split = 3)
+    int split;
+    int B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw;
+    int kh, kw, stride, pad, pixel_shuffle;
+    int per_sample, k_chunks, oi_major;
+    float gain;
+};
+
+// conv_wgrad_row3.hip: 0 if the geometry is not its own, 1 if it planned (and launched, unless plan_only), a negative MSG_E* code
+// on error.  *need = workspace floats of the launch it would make (0: no split).
+int conv_wgrad_row3_try(const WgradProblem& q, const void* gy, const void* x, float* gw, float* ws, long long ws_floats,
+                        int plan_only, long long* need, void* stream);
+// conv_wgrad.hip: the reduce for `n_out` results of `chunks` slabs each
+extern "C" int msg_wgrad_reduce_launch(const float* ws, float* gw, long long slab, int n_out, int chunks, int O, int taps,
+                                       int I, int ldgw, int oi_major, void* stream);

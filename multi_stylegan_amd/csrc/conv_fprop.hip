@@ -17,7 +17,7 @@
 // LDS rows are 128 B; 16-B slot s of row r lives at slot s ^ ((r >> 1) & 7), which makes both the ds_write_b128 of
 // the staging pass and the ds_read_b128 fragment reads conflict-free.  The epilogue goes through LDS so that each
 // lane stores 16 contiguous bytes.  bf16: v_mfma_f32_32x32x16_bf16; f32: v_mfma_f32_32x32x2_f32 (exact fp32).
-#include "msg_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
@@ -492,68 +492,106 @@ __global__ __launch_bounds__(256, LEAN ? LEAN : 2) void conv_fprop_kernel(const 
     }
 }
 
-extern "C" int msg_conv2d_fprop_pp_try(const void* x, const void* w, const float* bias, void* y,
-                                       int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                       int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                       long long w_batch_stride, const ActEpilogue* act, void* stream);
-
-extern "C" int msg_conv2d_fprop_pp_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
-                                            int kh, int kw, long long w_batch_stride);
-extern "C" int msg_conv2d_fprop_row3_try(const void* x, const void* w, const float* bias, void* y,
-                                         int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                         int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                         long long w_batch_stride, const ActEpilogue* act, void* stream);
-
-extern "C" int msg_conv2d_fprop_row3_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
-                                              int kh, int kw, long long w_batch_stride);
-extern "C" int msg_conv2d_fprop_upconv_try(const void* x, const void* w, const float* bias, void* y,
-                                           int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                           int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                           long long w_batch_stride, const ActEpilogue* act, void* stream);
-extern "C" int msg_conv2d_fprop_thin_try(const void* x, const void* w, const float* bias, void* y,
-                                         int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                         int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                         long long w_batch_stride, const ActEpilogue* act, void* stream);
-extern "C" int msg_conv2d_fprop_thin_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                              int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                              int act_mode);
-
-// Which kernel msg_conv2d_fprop would launch for this problem (the MSG_PLAN_* codes of msg_hip.h): THIN = the streaming kernels of
-// conv_thin.hip (1x1, <= 8 channels on one side; assuming no fused activation), ROW3 / ROW3N = conv_fprop_row3_kernel<4,4> / <2,2>
-// (3x3 'same' convs on wide maps, activation tile shared by the horizontal taps; 256x256 / 128x128 tile), PP = conv_fprop_pp_kernel
-// (256x256 ping-pong), DMA = conv_fprop_kernel<T, true> (128x128, LDS-DMA staging), REG = conv_fprop_kernel<T, false> (register
-// staging).
-extern "C" int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
-                                     int kh, int kw, long long w_batch_stride) {
-    if (dtype == MSG_BF16 && msg_conv2d_fprop_thin_eligible(B, IH, IW, Cx, Ck, OH, OW, N, N <= 8 ? 8 : (N + 7) / 8 * 8, kh, kw, 1,
-                                                            0, 1, 0, 0))
-        return MSG_PLAN_THIN;
-    if (dtype == MSG_BF16) {
-        const int r3 = msg_conv2d_fprop_row3_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
-        if (r3) return r3 == 1 ? MSG_PLAN_ROW3 : MSG_PLAN_ROW3N;
-    }
-    if (dtype == MSG_BF16 && msg_conv2d_fprop_pp_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride)) return MSG_PLAN_PP;
-    const int esz = dtype == MSG_BF16 ? 2 : 4;
-    const int n_iters = kh * kw * (Ck / (128 / esz));
+// The 128 x 128 kernel of this file takes what no other kernel wants; which instantiation, and its own limits.
+static ConvPlan conv_generic_select(const ConvProblem& q) {
+    const int n_iters = q.kh * q.kw * (q.Ck / (ROWB / q.esz()));
     static const int variant = msg_tunable("MSG_CONV_VARIANT", 0);
-    const bool fits31 = (long long)(w_batch_stride ? 1 : B) * IH * IW * Cx * esz < 0x7ffffff0ll &&
-                        (long long)N * kh * kw * Ck * esz < 0x7ffffff0ll;
-    return (fits31 && (variant == 1 || (variant == 0 && n_iters >= 8))) ? MSG_PLAN_DMA : MSG_PLAN_REG;
+    // staging: LDS-DMA (descriptor-addressed, msg_dma16) for long K sweeps, register staging (two steps in flight) for short ones;
+    // MSG_CONV_VARIANT=1 / 2 forces DMA / registers (A/B measurements)
+    // (the DMA instantiation addresses through 31-bit buffer offsets: the activations one descriptor spans -- the batch, or one
+    //  sample with per-sample weights -- and one weight set)
+    // (>= 8 K-steps since the pieces go through descriptors: 1x1 512->128 @64^2, B = 32: 39.3 -> 34.8 us; below that the register-
+    //  staged and lean instantiations stay ahead: 1x1 128->256 @256^2 532 vs 597 us)
+    const bool dma = q.fits31() && (variant == 1 || (variant == 0 && n_iters >= 8));
+    static const int lean_max = msg_tunable("MSG_CONV_LEAN", 4);                       // MSG_CONV_LEAN=<n>: lean variant for n_iters <= n (0 = never)
+    ConvPlan plan{CONV_REG, BM, BN, true};
+    // (split: register staging whatever the K length: the planes are written from the staging registers)
+    if (q.split) plan.kernel = CONV_REG_SPLIT;
+    else if (dma) plan.kernel = CONV_DMA;
+    else if (q.dtype == MSG_BF16 && n_iters <= lean_max) plan.kernel = CONV_REG_LEAN;
+    const long long mtot = q.mtot(), blocks = ((mtot + BM - 1) / BM) * ((q.N + BN - 1) / BN);
+    plan.supported = mtot < (1ll << 31) && blocks < (1ll << 31) &&
+                     (long long)(n_iters + 1) * ROWB + 128 <= 65536;                   // zero page covers a full K sweep
+    return plan;
 }
 
-static int conv2d_fprop_impl(const void* x, const void* w, const float* bias, void* y, int dtype,
-                             int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                             int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                             long long w_batch_stride, const ActEpilogue& act, void* stream);
+static void conv_generic_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, const float* bias, void* y,
+                                const ActEpilogue* act, void* stream) {
+    ConvParams p{};
+    conv_fill_common(p, q, act);
+    conv_fill_taps(p, q);
+    p.n_chunks = q.Ck / (ROWB / q.esz());
+    p.n_iters = q.kh * q.kw * p.n_chunks;
+    p.m_tiles = (int)((q.mtot() + BM - 1) / BM);
+    p.n_tiles = (q.N + BN - 1) / BN;
+    dim3 grid((unsigned)((long long)p.m_tiles * p.n_tiles), 1, q.samples());
+#define GENERIC(T, ...) hipLaunchKernelGGL((conv_fprop_kernel<T, __VA_ARGS__>), grid, dim3(256), 0, (hipStream_t)stream, \
+                                           (const T*)x, (const T*)w, (T*)y, bias, p)
+    const bool bf16 = q.dtype == MSG_BF16;
+    if (bf16 && plan.kernel == CONV_REG_LEAN) GENERIC(bf16_t, false, 3);
+    else if (bf16 && plan.kernel == CONV_DMA) GENERIC(bf16_t, true);
+    else if (bf16) GENERIC(bf16_t, false);
+    else if (plan.kernel == CONV_REG_SPLIT) GENERIC(float, false, 0, 3);
+    else if (plan.kernel == CONV_DMA) GENERIC(float, true);
+    else GENERIC(float, false);
+#undef GENERIC
+}
+
+// Which kernel runs a problem: the one place that knows the order.  The first kernel whose conditions all hold takes it.
+ConvPlan conv_fprop_select(const ConvProblem& q, const ActEpilogue* act, bool has_bias) {
+    ConvPlan plan;
+    if (conv_thin_eligible(q, act, &plan)) return plan;               // 1x1 convs with <= 8 channels on one side: streaming kernels
+    if (conv_upconv_eligible(q, act, has_bias, &plan)) return plan;   // the generator's sub-pixel up-convolution: activation-stationary kernel
+    if (conv_row3_eligible(q, act, has_bias, &plan)) return plan;     // 3x3 'same' convs on wide maps: activation tile shared by the three horizontal taps
+    if (conv_pp_eligible(q, &plan)) return plan;                      // large shapes: 256x256 ping-pong kernel
+    return conv_generic_select(q);
+}
+
+static ConvProblem conv_problem(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
+                                int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle, long long w_batch_stride) {
+    const int split = dtype == MSG_F32_SPLIT ? 3 : 0;      // fp32 storage, bf16 MFMA products (msg_hip.h)
+    return ConvProblem{split ? (int)MSG_F32 : dtype, split, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up, pixel_shuffle,
+                       w_batch_stride};
+}
+// What the queries that take the geometry alone assume about the rest: stride 1, the 'same' padding, no zero insertion, no
+// pixel shuffle, ldy = N rounded up to 8 (and, in msg_conv2d_fprop_plan, no bias and no epilogue).
+static ConvProblem conv_query_problem(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
+                                      long long w_batch_stride) {
+    return conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, N <= 8 ? 8 : (N + 7) / 8 * 8, kh, kw, 1, kh / 2, 1, 0, w_batch_stride);
+}
+
+// Which kernel msg_conv2d_fprop would launch for this problem (the MSG_PLAN_* codes of msg_hip.h): THIN = the streaming kernels of
+// conv_thin.hip (1x1, <= 8 channels on one side), ROW3 / ROW3N = conv_fprop_row3_kernel<4,4> / <2,2> (3x3 'same' convs on wide
+// maps, activation tile shared by the horizontal taps; 256x256 / 128x128 tile), PP = conv_fprop_pp_kernel (256x256 ping-pong),
+// DMA = conv_fprop_kernel<T, true> (128x128, LDS-DMA staging), REG = conv_fprop_kernel<T, false> (register staging: plain, lean
+// and split-bf16).  (The up-convolution kernel needs a pixel shuffle, which this query cannot express: it has no code.)
+extern "C" int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
+                                     int kh, int kw, long long w_batch_stride) {
+    switch (conv_fprop_select(conv_query_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride), nullptr, false).kernel) {
+        case CONV_THIN_N: case CONV_THIN_K: return MSG_PLAN_THIN;
+        case CONV_ROW3: return MSG_PLAN_ROW3;
+        case CONV_ROW3N: return MSG_PLAN_ROW3N;
+        case CONV_PP: return MSG_PLAN_PP;
+        case CONV_UPCONV: return MSG_PLAN_PP;      // (unreachable from this query -- no pixel shuffle; not a claim that up-conv is PP)
+        case CONV_DMA: return MSG_PLAN_DMA;
+        default: return MSG_PLAN_REG;
+    }
+}
+
+// (selected: the plan, where the caller had to ask for it already)
+static int conv2d_fprop_impl(const void* x, const void* w, const float* bias, void* y, const ConvProblem& q,
+                             const ActEpilogue& act, void* stream, const ConvPlan* selected = nullptr);
 
 extern "C" int msg_conv2d_fprop(const void* x, const void* w, const float* bias, void* y, int dtype,
                                 int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                                 int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
                                 long long w_batch_stride, void* stream) {
     ActEpilogue act{};
-    return conv2d_fprop_impl(x, w, bias, y, dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up,
-                             pixel_shuffle, w_batch_stride, act, stream);
+    return conv2d_fprop_impl(x, w, bias, y, conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up,
+                                                         pixel_shuffle, w_batch_stride), act, stream);
 }
+
+static bool is_row3(const ConvPlan& plan) { return plan.kernel == CONV_ROW3 || plan.kernel == CONV_ROW3N; }
 
 extern "C" int msg_conv2d_fprop_act_mask(const void* x, const void* w, void* y, int dtype,
                                          int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
@@ -561,15 +599,12 @@ extern "C" int msg_conv2d_fprop_act_mask(const void* x, const void* w, void* y, 
                                          const float* act_bias, const float* noise, const float* noise_weight,
                                          int noise_batch, float alpha, float scale, unsigned char* mask, void* stream) {
     if (noise && (!noise_weight || (noise_batch != 1 && noise_batch != B))) return MSG_EINVAL;
-    if (mask) {
-        // only the row-sharing 3x3 kernel writes the sign bytes: the caller asks msg_conv2d_fprop_plan first
-        const int plan = msg_conv2d_fprop_plan(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
-        if (dtype != MSG_BF16 || N % 8 || stride != 1 || pad != 1 || (plan != MSG_PLAN_ROW3 && plan != MSG_PLAN_ROW3N))
-            return MSG_EUNSUPPORTED;
-    }
+    const ConvProblem q = conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0, w_batch_stride);
     ActEpilogue act{act_bias, noise, noise_weight, noise_batch, 1, alpha, scale, nullptr, 0, 0.f, mask};
-    return conv2d_fprop_impl(x, w, nullptr, y, dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0,
-                             w_batch_stride, act, stream);
+    // only the row-sharing 3x3 kernel writes the sign bytes (the caller asks msg_conv2d_fprop_plan first)
+    if (!mask) return conv2d_fprop_impl(x, w, nullptr, y, q, act, stream);
+    const ConvPlan plan = conv_fprop_select(q, &act, false);
+    return is_row3(plan) ? conv2d_fprop_impl(x, w, nullptr, y, q, act, stream, &plan) : (int)MSG_EUNSUPPORTED;
 }
 
 extern "C" int msg_conv2d_fprop_act(const void* x, const void* w, void* y, int dtype,
@@ -588,32 +623,28 @@ extern "C" int msg_conv2d_fprop_residual(const void* x, const void* w, void* y, 
     if (!residual || res_ld < N || (((uintptr_t)residual) & 15u) || res_ld % (dtype == MSG_BF16 ? 8 : 4)) return MSG_EINVAL;
     ActEpilogue act{};
     act.enabled = 2; act.residual = residual; act.res_ld = res_ld; act.res_gain = gain;
-    return conv2d_fprop_impl(x, w, nullptr, y, dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0,
-                             w_batch_stride, act, stream);
+    return conv2d_fprop_impl(x, w, nullptr, y, conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0,
+                                                            w_batch_stride), act, stream);
 }
 
-extern "C" int msg_bias_act_reduce_launch(const float* part_b, float* grad_bias, int C, long long n_b, const float* part_n,
-                                          float* grad_nw, long long n_n, void* stream);
-
-// Partial-sum rows / entries of msg_conv2d_fprop_act_backward for this problem: rows of [N] floats (one per sample, pixel tile
-// and wave row of the row-sharing kernel) and noise entries (one per sample, tile and wave); 0 rows = the problem does not go to
-// that kernel (no fusion).
-static void act_backward_partials(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
-                                  long long w_batch_stride, long long* rows, long long* entries) {
+// Partial-sum rows / entries of msg_conv2d_fprop_act_backward for a problem that `plan` sends to the row-sharing kernel: rows of
+// [N] floats (one per sample, pixel tile and wave row) and noise entries (one per sample, tile and wave); 0 rows = the problem does
+// not go to that kernel (no fusion).
+static void act_backward_partials(const ConvProblem& q, const ConvPlan& plan, long long* rows, long long* entries) {
     *rows = *entries = 0;
-    const int plan = msg_conv2d_fprop_plan(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
-    if (dtype != MSG_BF16 || (plan != MSG_PLAN_ROW3 && plan != MSG_PLAN_ROW3N)) return;
-    const int hm = plan == MSG_PLAN_ROW3 ? 256 : 128;
-    const long long mtot = w_batch_stride ? (long long)OH * OW : (long long)B * OH * OW;
-    const long long tiles = (mtot / hm) * (w_batch_stride ? B : 1);
+    if (!is_row3(plan)) return;
+    const long long tiles = (q.mtot() / plan.tile_m) * q.samples();
     *rows = tiles * 2;
-    *entries = tiles * (N / hm) * 4;
+    *entries = tiles * (q.N / plan.tile_n) * 4;
 }
 
 extern "C" long long msg_conv2d_fprop_act_backward_workspace(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW,
                                                              int N, int kh, int kw, long long w_batch_stride, int has_noise) {
+    const ConvProblem q = conv_query_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
+    ActEpilogue act{};
+    act.enabled = 3;
     long long rows, entries;
-    act_backward_partials(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride, &rows, &entries);
+    act_backward_partials(q, conv_fprop_select(q, &act, false), &rows, &entries);
     return rows ? rows * N + (has_noise ? entries : 0) : 0;
 }
 
@@ -635,8 +666,12 @@ extern "C" int msg_conv2d_fprop_act_backward(const void* x, const void* w, void*
     if (!x || !w || !y || B < 0) return MSG_EINVAL;
     if (!sign_mask == !sign_map) return MSG_EINVAL;                         // exactly one sign source
     if (stride != 1 || pad != 1 || kh != 3 || kw != 3 || ldy != N) return MSG_EUNSUPPORTED;
+    const ConvProblem q = conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0, w_batch_stride);
+    ActEpilogue act{};
+    act.enabled = 3; act.alpha = alpha; act.scale = scale;
+    const ConvPlan plan = conv_fprop_select(q, &act, false);
     long long rows, entries;
-    act_backward_partials(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride, &rows, &entries);
+    act_backward_partials(q, plan, &rows, &entries);
     if (!rows) return MSG_EUNSUPPORTED;
     if (sign_mask && (mask_tile_m <= 0 || mask_tile_n <= 0 || mask_tile_n % 128 || N % mask_tile_n || (((uintptr_t)sign_mask) & 15u) ||
                       (mask_tile_m != 1 && mask_tile_m % 64) || ((long long)B * OH * OW) % mask_tile_m))
@@ -647,93 +682,37 @@ extern "C" int msg_conv2d_fprop_act_backward(const void* x, const void* w, void*
     if (has_noise && noise_batch != 1 && noise_batch != B) return MSG_EINVAL;
     const long long need_b = grad_bias ? rows * N : 0, need_n = has_noise ? entries : 0;
     if (need_b + need_n > 0 && (!ws || ws_floats < need_b + need_n)) return MSG_EINVAL;
-    ActEpilogue act{};
-    act.enabled = 3; act.alpha = alpha; act.scale = scale;
     act.residual = residual; act.res_ld = res_ld; act.res_gain = 1.f;
     act.mask = const_cast<unsigned char*>(sign_mask); act.mask_tile_m = mask_tile_m; act.mask_tile_n = mask_tile_n;
     act.sign_src = sign_map; act.sign_ld = sign_ld;
     act.noise = has_noise ? noise : nullptr; act.noise_batch = noise_batch;
     act.part_b = grad_bias ? ws : nullptr;
     act.part_n = has_noise ? ws + need_b : nullptr;
-    if (!msg_conv2d_fprop_row3_try(x, w, nullptr, y, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0, w_batch_stride,
-                                   &act, stream))
-        return MSG_EUNSUPPORTED;
+    conv_row3_launch(q, plan, x, w, nullptr, y, &act, stream);
     if (MSG_CHECK_LAUNCH() != MSG_OK) return MSG_ELAUNCH;
     return msg_bias_act_reduce_launch(act.part_b, grad_bias, N, rows, act.part_n, grad_noise_weight, entries, stream);
 }
 
-static int conv2d_fprop_impl(const void* x, const void* w, const float* bias, void* y, int dtype,
-                             int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                             int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                             long long w_batch_stride, const ActEpilogue& act, void* stream) {
-    if (B == 0) return MSG_OK;
-    if (!x || !w || !y || B < 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || N <= 0 || kh <= 0 || kw <= 0 ||
-        stride <= 0 || in_up <= 0 || Cx <= 0 || Ck <= 0 || ldy <= 0)
+static int conv2d_fprop_impl(const void* x, const void* w, const float* bias, void* y, const ConvProblem& q,
+                             const ActEpilogue& act, void* stream, const ConvPlan* selected) {
+    if (q.B == 0) return MSG_OK;
+    if (!x || !w || !y || q.B < 0 || q.IH <= 0 || q.IW <= 0 || q.OH <= 0 || q.OW <= 0 || q.N <= 0 || q.kh <= 0 || q.kw <= 0 ||
+        q.stride <= 0 || q.in_up <= 0 || q.Cx <= 0 || q.Ck <= 0 || q.ldy <= 0)
         return MSG_EINVAL;
-    const int split = dtype == MSG_F32_SPLIT ? 3 : 0;      // fp32 storage, bf16 MFMA products (msg_hip.h)
-    if (split) dtype = MSG_F32;
-    if (dtype != MSG_F32 && dtype != MSG_BF16) return MSG_EUNSUPPORTED;
-    const int esz = dtype == MSG_BF16 ? 2 : 4, vec = 16 / esz, bke = 128 / esz;
-    if (Ck % bke || Cx % vec || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15u)) return MSG_EUNSUPPORTED;
-    if (pixel_shuffle && (N % 4 || (N / 4) % vec || ldy % vec)) return MSG_EUNSUPPORTED;
-    if (!pixel_shuffle && ldy % vec) return MSG_EUNSUPPORTED;
-    if (in_up > 1 && stride != 1) return MSG_EUNSUPPORTED;
-    if (dtype == MSG_BF16 &&
-        msg_conv2d_fprop_thin_try(x, w, bias, y, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up, pixel_shuffle,
-                                  w_batch_stride, &act, stream))
-        return MSG_CHECK_LAUNCH();                 // 1x1 convs with <= 8 channels on one side: streaming kernels (conv_thin.hip)
-    if (dtype == MSG_BF16 &&
-        msg_conv2d_fprop_upconv_try(x, w, bias, y, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up,
-                                    pixel_shuffle, w_batch_stride, &act, stream))
-        return MSG_CHECK_LAUNCH();                 // the generator's sub-pixel up-convolution: activation-stationary kernel
-    if (dtype == MSG_BF16 &&
-        msg_conv2d_fprop_row3_try(x, w, bias, y, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up,
-                                  pixel_shuffle, w_batch_stride, &act, stream))
-        return MSG_CHECK_LAUNCH();                 // 3x3 'same' convs on wide maps: activation tile shared by the three horizontal taps
-    if (dtype == MSG_BF16 &&
-        msg_conv2d_fprop_pp_try(x, w, bias, y, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up,
-                                pixel_shuffle, w_batch_stride, &act, stream))
-        return MSG_CHECK_LAUNCH();                 // large shapes: 256x256 ping-pong kernel (conv_fprop_pp.hip)
-    ConvParams p{};
-    p.B = B; p.IH = IH; p.IW = IW; p.Cx = Cx; p.Ck = Ck; p.OH = OH; p.OW = OW; p.N = N; p.ldy = ldy;
-    p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad; p.in_up = in_up; p.pixel_shuffle = pixel_shuffle;
-    p.per_sample = w_batch_stride != 0;
-    p.act = act;
-    p.x_bstride = (long long)IH * IW * Cx;
-    p.w_bstride = w_batch_stride;
-    p.y_bstride = pixel_shuffle ? 4ll * OH * OW * ldy : (long long)OH * OW * ldy;
-    const long long mtot = p.per_sample ? (long long)OH * OW : (long long)B * OH * OW;
-    if (mtot >= (1ll << 31)) return MSG_EUNSUPPORTED;
-    p.Mtot = (int)mtot;
-    p.n_chunks = Ck / bke;
-    p.n_iters = kh * kw * p.n_chunks;
-    if ((long long)(p.n_iters + 1) * ROWB + 128 > 65536) return MSG_EUNSUPPORTED;   // zero page covers a full K sweep
-    p.m_tiles = (int)((mtot + BM - 1) / BM);
-    p.n_tiles = (N + BN - 1) / BN;
-    const long long blocks = (long long)p.m_tiles * p.n_tiles;
-    if (blocks >= (1ll << 31)) return MSG_EUNSUPPORTED;
-    dim3 grid((unsigned)blocks, 1, p.per_sample ? B : 1);
-    hipStream_t s = (hipStream_t)stream;
-    static const int variant = msg_tunable("MSG_CONV_VARIANT", 0);
-    // staging: LDS-DMA (descriptor-addressed, msg_dma16) for long K sweeps, register staging (two steps in flight) for short ones;
-    // MSG_CONV_VARIANT=1 / 2 forces DMA / registers (A/B measurements)
-    // (the DMA instantiation addresses through 31-bit buffer offsets: the activations one descriptor spans -- the batch, or one
-    //  sample with per-sample weights -- and one weight set)
-    const bool fits31 = (long long)(p.per_sample ? 1 : B) * p.x_bstride * esz < 0x7ffffff0ll &&
-                        (long long)N * kh * kw * Ck * esz < 0x7ffffff0ll;
-    // (>= 8 K-steps since the pieces go through descriptors: 1x1 512->128 @64^2, B = 32: 39.3 -> 34.8 us; below that the register-
-    //  staged and lean instantiations stay ahead: 1x1 128->256 @256^2 532 vs 597 us)
-    const bool dma = fits31 && (variant == 1 || (variant == 0 && p.n_iters >= 8));
-    static const int lean_max = msg_tunable("MSG_CONV_LEAN", 4);                       // MSG_CONV_LEAN=<n>: lean variant for n_iters <= n (0 = never)
-    if (dtype == MSG_BF16) {
-        if (!dma && p.n_iters <= lean_max) hipLaunchKernelGGL((conv_fprop_kernel<bf16_t, false, 3>), grid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, bias, p);
-        else if (dma) hipLaunchKernelGGL((conv_fprop_kernel<bf16_t, true>), grid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, bias, p);
-        else hipLaunchKernelGGL((conv_fprop_kernel<bf16_t, false>), grid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, bias, p);
-    } else if (split == 3) {       // (register staging whatever the K length: the planes are written from the staging registers)
-        hipLaunchKernelGGL((conv_fprop_kernel<float, false, 0, 3>), grid, dim3(256), 0, s, (const float*)x, (const float*)w, (float*)y, bias, p);
-    } else {
-        if (dma) hipLaunchKernelGGL((conv_fprop_kernel<float, true>), grid, dim3(256), 0, s, (const float*)x, (const float*)w, (float*)y, bias, p);
-        else hipLaunchKernelGGL((conv_fprop_kernel<float, false>), grid, dim3(256), 0, s, (const float*)x, (const float*)w, (float*)y, bias, p);
+    if (q.dtype != MSG_F32 && q.dtype != MSG_BF16) return MSG_EUNSUPPORTED;
+    const int vec = 16 / q.esz(), bke = ROWB / q.esz();      // elements per 16-byte vector / per 128-byte K run
+    if (q.Ck % bke || q.Cx % vec || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15u)) return MSG_EUNSUPPORTED;
+    if (q.ldy % vec || (q.pixel_shuffle && (q.N % 4 || (q.N / 4) % vec))) return MSG_EUNSUPPORTED;
+    if (q.in_up > 1 && q.stride != 1) return MSG_EUNSUPPORTED;
+    const ConvPlan plan = selected ? *selected : conv_fprop_select(q, &act, bias != nullptr);
+    if (!plan.supported) return MSG_EUNSUPPORTED;
+    switch (plan.kernel) {
+        case CONV_THIN_N: case CONV_THIN_K: conv_thin_launch(q, plan, x, w, bias, y, &act, stream); break;
+        case CONV_UPCONV: conv_upconv_launch(q, plan, x, w, y, stream); break;
+        case CONV_ROW3: case CONV_ROW3N: conv_row3_launch(q, plan, x, w, bias, y, &act, stream); break;
+        case CONV_PP: conv_pp_launch(q, plan, x, w, bias, y, &act, stream); break;
+        case CONV_DMA: case CONV_REG: case CONV_REG_LEAN: case CONV_REG_SPLIT:
+            conv_generic_launch(q, plan, x, w, bias, y, &act, stream); break;
     }
     return MSG_CHECK_LAUNCH();
 }

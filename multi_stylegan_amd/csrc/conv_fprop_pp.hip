@@ -27,7 +27,7 @@
 //   group 1 (w>=4)   MFMA h1(t-1) read h0(t) MFMA h0  read h1   MFMA h1(t)  ...
 //   DMA(t+1) is issued at the top of each wave's "read h0(t)" phase and retired before the barrier that ends slot
 //   4t+3; the stage it fills was last read in slot 4t-1, and read phases drain lgkmcnt before their barrier.
-#include "msg_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
@@ -393,52 +393,36 @@ __global__ __launch_bounds__(512, 2) void conv_fprop_pp_kernel(const bf16_t* __r
     PP_CLOCK(3);
 }
 
-// Which shapes take the large tile (shared by the launcher below and by msg_conv2d_fprop_plan).
-extern "C" int msg_conv2d_fprop_pp_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
-                                            int kh, int kw, long long w_batch_stride) {
+// Which shapes take the large tile.
+bool conv_pp_eligible(const ConvProblem& q, ConvPlan* plan) {
     static const int enabled = msg_tunable("MSG_CONV_PP", 1);
-    if (!enabled) return 0;
-    const bool per_sample = w_batch_stride != 0;
-    const long long mtot = per_sample ? (long long)OH * OW : (long long)B * OH * OW;
-    const int n_iters = kh * kw * (Ck / 64);
-    if (N < 256 || mtot < 1024 || n_iters < 4 || mtot >= (1ll << 31)) return 0;
+    if (!enabled || q.dtype != MSG_BF16) return false;
+    const long long mtot = q.mtot();
+    const int N = q.N, n_iters = q.kh * q.kw * (q.Ck / 64);
+    if (N < 256 || mtot < 1024 || n_iters < 4 || mtot >= (1ll << 31)) return false;
     // output-channel counts that leave a mostly empty last 256-column tile (N = 384: 1.5 tiles, a third of the MFMA
     // work on padding) run faster on the 128-wide tile: 256->384 @128^2 532 vs 660 us
-    if ((long long)((N + PN - 1) / PN) * PN * 100 > (long long)N * 115) return 0;
-    if ((long long)(n_iters + 1) * PROW + 128 > 65536) return 0;
+    if ((long long)((N + PN - 1) / PN) * PN * 100 > (long long)N * 115) return false;
+    if ((long long)(n_iters + 1) * PROW + 128 > 65536) return false;
     // 31-bit buffer offsets: the activations of one launch (of one sample with per-sample weights) and one weight set
-    if ((long long)(per_sample ? 1 : B) * IH * IW * Cx * 2 >= 0x7ffffff0ll || (long long)N * kh * kw * Ck * 2 >= 0x7ffffff0ll) return 0;
+    if (!q.fits31()) return false;
     const long long blocks = ((mtot + PM - 1) / PM) * ((N + PN - 1) / PN);
-    if (blocks >= (1ll << 31)) return 0;
-    if (blocks * (per_sample ? B : 1) < 224) return 0;      // one workgroup per CU: small grids belong to the 128-tile kernel
-    return 1;
+    if (blocks >= (1ll << 31)) return false;
+    if (blocks * q.samples() < 224) return false;      // one workgroup per CU: small grids belong to the 128-tile kernel
+    *plan = ConvPlan{CONV_PP, PM, PN, true};
+    return true;
 }
 
-// Called by msg_conv2d_fprop (conv_fprop.hip) for shapes where the large tile pays; returns 1 if it launched.
-extern "C" int msg_conv2d_fprop_pp_try(const void* x, const void* w, const float* bias, void* y,
-                                       int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                       int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                       long long w_batch_stride, const ActEpilogue* act, void* stream) {
-    if (!msg_conv2d_fprop_pp_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride)) return 0;
-    const bool per_sample = w_batch_stride != 0;
-    const long long mtot = per_sample ? (long long)OH * OW : (long long)B * OH * OW;
-    const int n_iters = kh * kw * (Ck / 64);
+void conv_pp_launch(const ConvProblem& q, const ConvPlan&, const void* x, const void* w, const float* bias, void* y,
+                    const ActEpilogue* act, void* stream) {
     ConvParamsPP p{};
-    p.B = B; p.IH = IH; p.IW = IW; p.Cx = Cx; p.Ck = Ck; p.OH = OH; p.OW = OW; p.N = N; p.ldy = ldy;
-    p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad; p.in_up = in_up; p.pixel_shuffle = pixel_shuffle;
-    p.per_sample = per_sample;
-    if (act) p.act = *act;
-    p.x_bstride = (long long)IH * IW * Cx;
-    p.w_bstride = w_batch_stride;
-    p.y_bstride = pixel_shuffle ? 4ll * OH * OW * ldy : (long long)OH * OW * ldy;
-    p.Mtot = (int)mtot;
-    p.n_chunks = Ck / 64;
-    p.n_iters = n_iters;
-    p.m_tiles = (int)((mtot + PM - 1) / PM);
-    p.n_tiles = (N + PN - 1) / PN;
-    const long long blocks = (long long)p.m_tiles * p.n_tiles;
-    dim3 grid((unsigned)blocks, 1, per_sample ? B : 1);
+    conv_fill_common(p, q, act);
+    conv_fill_taps(p, q);
+    p.n_chunks = q.Ck / 64;
+    p.n_iters = q.kh * q.kw * p.n_chunks;
+    p.m_tiles = (int)((q.mtot() + PM - 1) / PM);
+    p.n_tiles = (q.N + PN - 1) / PN;
+    dim3 grid((unsigned)((long long)p.m_tiles * p.n_tiles), 1, q.samples());
     hipLaunchKernelGGL(conv_fprop_pp_kernel, grid, dim3(512), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w,
                        (bf16_t*)y, bias, p);
-    return 1;
 }

@@ -21,7 +21,7 @@
 // An output tile is 256 consecutive pixels = one or more whole image-row segments (map width 64, 128, or a multiple of
 // 256); segment s occupies LDS rows s*(len+2) .. s*(len+2)+len+1, i.e. output pixel p of segment s, tap kw, reads row
 // p + kw + 2 s.
-#include "msg_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 1) void conv_fprop_row3_kernel(c
     constexpr int NP = 64 / RPP;                                // passes per half patch (64 rows): 16 / 8
     const int er = lane / LPR, u16 = lane % LPR, ec = u16 * VEC;
     const int n = n0 + wn * WN + ec;
-    // Eligibility (msg_conv2d_fprop_row3_eligible) leaves whole tiles only -- Mtot % HM == 0, N % HN == 0 -- and the output row of
+    // Eligibility (conv_row3_eligible) leaves whole tiles only -- Mtot % HM == 0, N % HN == 0 -- and the output row of
     // pixel m is row m: no bounds predicates and no coordinates here.  (One wave per SIMD: every epilogue instruction is four
     // cycles that nothing overlaps; the stepped (b, oh, ow) coordinates and 16 predicated stores per half were a third of them.)
     // half-patches of 64 rows: all rows / residual vectors of a half requested before any is used
@@ -656,14 +656,15 @@ static int row3_tile_columns(int N) {
     return 0;
 }
 
-// Which problems take this kernel (shared by the launcher below and by msg_conv2d_fprop_plan): a 3x3 convolution whose
-// output map equals its input map is the stride-1, pad-1, no-zero-insertion 'same' convolution.
-extern "C" int msg_conv2d_fprop_row3_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
-                                              int kh, int kw, long long w_batch_stride) {
+// Which problems take this kernel, and on which tile: a 3x3 convolution whose output map equals its input map, at stride 1 and
+// padding 1 without zero insertion, is the 'same' convolution.  The activation-backward epilogue (enabled == 3) has no bias.
+bool conv_row3_eligible(const ConvProblem& q, const ActEpilogue* act, bool has_bias, ConvPlan* plan) {
     static const int enabled = msg_tunable("MSG_CONV_ROW3", 1);
-    if (!enabled || kh != 3 || kw != 3 || IH != OH || IW != OW || Ck % 64 || Cx % 64) return 0;
-    const bool per_sample = w_batch_stride != 0;
-    const long long mtot = per_sample ? (long long)OH * OW : (long long)B * OH * OW;
+    const int IH = q.IH, IW = q.IW, Cx = q.Cx, Ck = q.Ck, OH = q.OH, OW = q.OW, N = q.N;
+    if (q.dtype != MSG_BF16 || q.stride != 1 || q.pad != 1 || q.in_up != 1 || q.pixel_shuffle) return false;
+    if (!enabled || q.kh != 3 || q.kw != 3 || IH != OH || IW != OW || Ck % 64 || Cx % 64) return false;
+    if (conv_act_mode(act) == 3 && has_bias) return false;
+    const long long mtot = q.mtot();
     // The 128 x 128 variant (two workgroups per CU) takes the layers with 128 / 384 output channels from the plain 128x128
     // kernel: 3x3 128->128 @256^2 516 -> 476 us, 256->128 @256^2 866 -> 819, 256->384 @128^2 650 -> 614, 384->384 @64^2
     // 235 -> 205.  MSG_CONV_ROW3_NARROW=0 switches it off (A/B).
@@ -681,78 +682,50 @@ extern "C" int msg_conv2d_fprop_row3_eligible(int B, int IH, int IW, int Cx, int
     static const int shortk = msg_tunable("MSG_CONV_ROW3_SHORTK", 128);
     if (hn == 256 && Ck <= shortk && N % 128 == 0) hn = 128;
     if (OW == 32 && w32 && N >= 128 && (long long)((N + 127) / 128) * 128 * 100 <= (long long)N * 115) hn = 128;
-    if (!hn || (hn == 128 && !narrow) || N % hn) return 0;
+    if (!hn || (hn == 128 && !narrow) || N % hn) return false;
     const int hm = hn;                             // square tiles: 256 x 256 or 128 x 128
-    if (!((OW >= 64 && hm % OW == 0) || OW % hm == 0 || (OW == 32 && hm == 128))) return 0;   // whole image-row segments per tile, <= 8 halo rows
-    if (mtot < 1024 || mtot >= (1ll << 31) || mtot % hm) return 0;
-    const long long x_bytes = (long long)(per_sample ? 1 : B) * IH * IW * Cx * 2;
-    const long long w_bytes = (long long)N * 9 * Ck * 2;
-    if (x_bytes >= 0x7ffffff0ll || w_bytes >= 0x7ffffff0ll) return 0;                   // 31-bit buffer offsets
-    if ((long long)9 * (Ck / 64) * HROW >= (1ll << 24)) return 0;
+    if (!((OW >= 64 && hm % OW == 0) || OW % hm == 0 || (OW == 32 && hm == 128))) return false;   // whole image-row segments per tile, <= 8 halo rows
+    if (mtot < 1024 || mtot >= (1ll << 31) || mtot % hm) return false;
+    if (!q.fits31()) return false;                                                      // 31-bit buffer offsets
+    if ((long long)9 * (Ck / 64) * HROW >= (1ll << 24)) return false;
     const long long blocks = (mtot / hm) * ((N + hn - 1) / hn);
-    if (blocks * (per_sample ? B : 1) < (hm == 256 ? 224 : 448) || blocks >= (1ll << 31)) return 0;
-    return hm == 256 ? 1 : 2;                      // 1: 256 x 256 tile, 2: 128 x 128 tile
+    if (blocks * q.samples() < (hm == 256 ? 224 : 448) || blocks >= (1ll << 31)) return false;
+    // the kernel's division by the segment length: row / (seg_len + 2) == (row * seg_magic) >> 16 for every buffer row
+    // (cannot fail for rows < 2^8 * 2; were it to, the plain kernels take the problem)
+    const int seg_len = OW < hm ? OW : hm, seg_magic = 65536 / (seg_len + 2) + 1;
+    for (int row = 0; row < hm + 16; ++row)
+        if (((row * seg_magic) >> 16) != row / (seg_len + 2)) return false;
+    *plan = ConvPlan{hm == 256 ? CONV_ROW3 : CONV_ROW3N, hm, hn, true};
+    return true;
 }
 
-// Called by msg_conv2d_fprop (conv_fprop.hip) before the other large-tile kernels; returns 1 if it launched.
-extern "C" int msg_conv2d_fprop_row3_try(const void* x, const void* w, const float* bias, void* y,
-                                         int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                         int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                         long long w_batch_stride, const ActEpilogue* act, void* stream) {
-    if (stride != 1 || pad != 1 || in_up != 1 || pixel_shuffle ||
-        !msg_conv2d_fprop_row3_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride))
-        return 0;
-    const bool per_sample = w_batch_stride != 0;
-    const long long mtot = per_sample ? (long long)OH * OW : (long long)B * OH * OW;
-    const int n_chunks = Ck / 64;
+void conv_row3_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, const float* bias, void* y,
+                      const ActEpilogue* act, void* stream) {
+    const int hm = plan.tile_m, hn = plan.tile_n, n_chunks = q.Ck / 64;
     ConvParamsR3 p{};
-    p.B = B; p.IH = IH; p.IW = IW; p.Cx = Cx; p.Ck = Ck; p.OH = OH; p.OW = OW; p.N = N; p.ldy = ldy;
-    p.per_sample = per_sample;
-    const int hn = msg_conv2d_fprop_row3_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride) == 1 ? 256 : 128, hm = hn;
-    p.seg_len = OW < hm ? OW : hm;
+    conv_fill_common(p, q, act);
+    p.seg_len = q.OW < hm ? q.OW : hm;
     p.n_seg = hm / p.seg_len;
-    if (act) p.act = *act;
-    p.x_bstride = (long long)IH * IW * Cx;
-    p.w_bstride = w_batch_stride;
-    p.y_bstride = (long long)OH * OW * ldy;
-    p.Mtot = (int)mtot;
     p.n_chunks = n_chunks;
     p.n_iters = 9 * n_chunks;
-    p.m_tiles = (int)(mtot / hm);
+    p.m_tiles = (int)(q.mtot() / hm);
     p.seg_magic = 65536 / (p.seg_len + 2) + 1;
-    for (int row = 0; row < hm + 16; ++row)
-        if (((row * p.seg_magic) >> 16) != row / (p.seg_len + 2)) return 0;      // (cannot happen for rows < 2^8 * 2; the plain kernels take it)
     auto log2_exact = [](long long v) { int sh = 0; while ((1ll << sh) < v) ++sh; return (1ll << sh) == v ? sh : -1; };
-    p.ow_shift = log2_exact(OW);
-    p.ohw_shift = log2_exact((long long)OH * OW);
+    p.ow_shift = log2_exact(q.OW);
+    p.ohw_shift = log2_exact((long long)q.OH * q.OW);
     if (p.ohw_shift < 0) p.ow_shift = -1;
-    p.n_tiles = (N + hn - 1) / hn;
-    const long long blocks = (long long)p.m_tiles * p.n_tiles;
-    dim3 grid((unsigned)blocks, 1, per_sample ? B : 1);
+    p.n_tiles = (q.N + hn - 1) / hn;
+    dim3 grid((unsigned)((long long)p.m_tiles * p.n_tiles), 1, q.samples());
     // MSG_CONV_ROW3_S16=0: the 256 x 256 tile on v_mfma_f32_32x32x16_bf16 (A/B)
     static const int s16 = msg_tunable("MSG_CONV_ROW3_S16", 1);
     static const int s16n = msg_tunable("MSG_CONV_ROW3N_S16", 1);    // (the 128 x 128 tile: +2..6 %)
-    if (p.act.enabled == 3) {
-        if (bias) return 0;
-        if (hn == 256)
-            hipLaunchKernelGGL((conv_fprop_row3_kernel<4, 4, true, 1>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)w, (bf16_t*)y, bias, p);
-        else
-            hipLaunchKernelGGL((conv_fprop_row3_kernel<2, 2, true, 1>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)w, (bf16_t*)y, bias, p);
-        return 1;
-    }
-    if (hn == 256 && s16)
-        hipLaunchKernelGGL((conv_fprop_row3_kernel<4, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)w, (bf16_t*)y, bias, p);
-    else if (hn == 256)
-        hipLaunchKernelGGL((conv_fprop_row3_kernel<4, 4, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)w, (bf16_t*)y, bias, p);
-    else if (s16n)
-        hipLaunchKernelGGL((conv_fprop_row3_kernel<2, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)w, (bf16_t*)y, bias, p);
-    else
-        hipLaunchKernelGGL((conv_fprop_row3_kernel<2, 2, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)w, (bf16_t*)y, bias, p);
-    return 1;
+#define ROW3(...) hipLaunchKernelGGL((conv_fprop_row3_kernel<__VA_ARGS__>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, \
+                                     (const bf16_t*)w, (bf16_t*)y, bias, p)
+    if (p.act.enabled == 3 && hn == 256) ROW3(4, 4, true, 1);
+    else if (p.act.enabled == 3) ROW3(2, 2, true, 1);
+    else if (hn == 256 && s16) ROW3(4, 4, true);
+    else if (hn == 256) ROW3(4, 4, false);
+    else if (s16n) ROW3(2, 2, true);
+    else ROW3(2, 2, false);
+#undef ROW3
 }

@@ -17,7 +17,7 @@
 //
 // Both take shared or per-sample weights (grid.y = sample) in the image layout of the other forward kernels
 // ([N][taps = 1][Ck], K-contiguous) and the bias / residual-merge epilogues their callers use.
-#include "msg_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
@@ -221,94 +221,104 @@ __global__ __launch_bounds__(256) void conv_thin_k_sload_kernel(const bf16_t* __
     }
 }
 
-static int thin_enabled() {
-    static const int v = msg_tunable("MSG_CONV_THIN", 1);
-    return v;
-}
-
-// 1: thin N, 2: thin K, 0: neither.  (1x1, stride 1, no padding, no zero insertion is implied by kh = kw = 1 and equal maps.)
-extern "C" int msg_conv2d_fprop_thin_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                              int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                              int act_mode) {
-    if (!thin_enabled() || kh != 1 || kw != 1 || stride != 1 || pad != 0 || in_up != 1 || pixel_shuffle || IH != OH ||
-        IW != OW || B <= 0)
+// All the conditions of the two kernels: mode 1 = thin N, 2 = thin K, 0 = neither.  (1x1, stride 1, no padding, no zero insertion
+// is implied by kh = kw = 1 and equal maps.)
+static int thin_mode(const ConvProblem& q, int act_mode) {
+    static const int enabled = msg_tunable("MSG_CONV_THIN", 1);
+    if (!enabled || q.kh != 1 || q.kw != 1 || q.stride != 1 || q.pad != 0 || q.in_up != 1 || q.pixel_shuffle || q.IH != q.OH ||
+        q.IW != q.OW || q.B <= 0)
         return 0;
-    const long long m = (long long)B * OH * OW;
+    const long long m = (long long)q.B * q.OH * q.OW;
     if (m < 4096) return 0;                                          // (tiny maps: launch-bound either way)
-    if (N <= 8 && act_mode == 0 && ldy == 8 && Ck % 32 == 0 && Ck <= 512 && Cx >= Ck && Cx % 8 == 0) return 1;
-    if (Cx == 8 && (act_mode == 0 || act_mode == 2) && N % 8 == 0 && N >= 64 && N <= 512 && 64 % (N / 8) == 0 && ldy % 8 == 0 &&
-        Ck >= 8)
+    if (q.samples() > 65535) return 0;                               // grid.y
+    // thin N is instantiated for Ck / 32 in {2, 4, 6, 8, 12, 16} (the channel counts the models have): the rest of
+    // "Ck % 32 == 0, Ck <= 512" goes to the tile kernels
+    const int kc = q.Ck / 32;
+    if (q.N <= 8 && act_mode == 0 && q.ldy == 8 && q.Ck % 32 == 0 && q.Ck <= 512 && q.Cx >= q.Ck && q.Cx % 8 == 0 &&
+        (kc == 2 || kc == 4 || kc == 6 || kc == 8 || kc == 12 || kc == 16))
+        return 1;
+    if (q.Cx == 8 && (act_mode == 0 || act_mode == 2) && q.N % 8 == 0 && q.N >= 64 && q.N <= 512 && 64 % (q.N / 8) == 0 &&
+        q.ldy % 8 == 0 && q.Ck >= 8)
         return 2;
     return 0;
 }
 
-extern "C" int msg_conv2d_fprop_thin_try(const void* x, const void* w, const float* bias, void* y,
-                                         int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                         int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                         long long w_batch_stride, const ActEpilogue* act, void* stream) {
-    const int mode = msg_conv2d_fprop_thin_eligible(B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up,
-                                                    pixel_shuffle, act ? act->enabled : 0);
-    if (!mode) return 0;
-    const bool per_sample = w_batch_stride != 0;
+// Workgroups per sample, and the pixel groups each wave takes: enough waves to fill the chip a few times over, each amortising
+// its weight registers over several groups.
+constexpr int THIN_K_U = 8;                                          // (8 pixels in flight per lane: 307 / 159 / 152 us against 321 / 171 / 158 with 4)
+static long long thin_grid(const ConvProblem& q, bool thin_n, int* groups_per_wave) {
+    const int ppw = thin_n ? 16 : 64 / (q.N / 8);
+    const long long groups = (q.mtot() + ppw - 1) / ppw;
+    const int per = thin_n ? 8192 : 16384, lo = thin_n ? 1 : THIN_K_U, hi = thin_n ? 8 : 32;
+    int g = (int)((groups * q.samples() + per - 1) / per);
+    if (!thin_n) g = (g + THIN_K_U - 1) / THIN_K_U * THIN_K_U;       // (whole steps of U pixels in flight)
+    *groups_per_wave = g = g < lo ? lo : g > hi ? hi : g;
+    return (groups + 4ll * g - 1) / (4ll * g);
+}
+
+bool conv_thin_eligible(const ConvProblem& q, const ActEpilogue* act, ConvPlan* plan) {
+    if (q.dtype != MSG_BF16) return false;
+    const int mode = thin_mode(q, conv_act_mode(act));
+    if (!mode) return false;
+    int groups_per_wave;
+    if (thin_grid(q, mode == 1, &groups_per_wave) >= (1ll << 31)) return false;
+    *plan = ConvPlan{mode == 1 ? CONV_THIN_N : CONV_THIN_K, 0, 0, true};
+    return true;
+}
+
+// (the public query has no weight stride and no dtype: shared weights, bf16)
+extern "C" int msg_conv2d_fprop_thin_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
+                                              int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
+                                              int act_mode) {
+    const ConvProblem q{MSG_BF16, 0, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up, pixel_shuffle, 0};
+    ActEpilogue act{};
+    act.enabled = act_mode;
+    ConvPlan plan;
+    return conv_thin_eligible(q, &act, &plan) ? (plan.kernel == CONV_THIN_N ? 1 : 2) : 0;
+}
+
+void conv_thin_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, const float* bias, void* y,
+                      const ActEpilogue* act, void* stream) {
+    const bool per_sample = q.per_sample();
     ThinParams p{};
-    p.M = per_sample ? (long long)OH * OW : (long long)B * OH * OW;
-    p.Cx = Cx; p.Ck = Ck; p.N = N; p.ldy = ldy;
-    p.x_bstride = per_sample ? (long long)IH * IW * Cx : 0;
-    p.w_bstride = w_batch_stride;
-    p.y_bstride = per_sample ? (long long)OH * OW * ldy : 0;
+    p.M = q.mtot();
+    p.Cx = q.Cx; p.Ck = q.Ck; p.N = q.N; p.ldy = q.ldy;
+    p.x_bstride = per_sample ? q.x_bstride() : 0;
+    p.w_bstride = q.w_batch_stride;
+    p.y_bstride = per_sample ? q.y_bstride() : 0;
     p.bias = bias;
     if (act && act->enabled == 2) {
         p.residual = act->residual; p.res_ld = act->res_ld; p.res_gain = act->res_gain;
-        p.res_bstride = per_sample ? (long long)OH * OW * act->res_ld : 0;
+        p.res_bstride = per_sample ? (long long)q.OH * q.OW * act->res_ld : 0;
     }
-    const int samples = per_sample ? B : 1;
+    const int samples = q.samples();
     hipStream_t s = (hipStream_t)stream;
     const bf16_t* xp = (const bf16_t*)x;
     const bf16_t* wp = (const bf16_t*)w;
     bf16_t* yp = (bf16_t*)y;
-    if (mode == 1) {
-        const long long groups = (p.M + 15) / 16;
-        // enough waves to fill the chip a few times over, each amortising its weight registers over several pixel groups
-        p.groups_per_wave = (int)((groups * samples + 8191) / 8192);
-        if (p.groups_per_wave < 1) p.groups_per_wave = 1;
-        if (p.groups_per_wave > 8) p.groups_per_wave = 8;
-        const long long blocks = (groups + 4ll * p.groups_per_wave - 1) / (4ll * p.groups_per_wave);
-        if (blocks >= (1ll << 31) || samples > 65535) return 0;
-        dim3 grid((unsigned)blocks, samples);
-        switch (Ck / 32) {
+    if (plan.kernel == CONV_THIN_N) {
+        dim3 grid((unsigned)thin_grid(q, true, &p.groups_per_wave), samples);
+        switch (q.Ck / 32) {
 #define THIN_N(KC_) case KC_: hipLaunchKernelGGL((conv_thin_n_kernel<KC_>), grid, dim3(256), 0, s, xp, wp, yp, p); break
             THIN_N(2); THIN_N(4); THIN_N(6); THIN_N(8); THIN_N(12); THIN_N(16);
 #undef THIN_N
-            default: return 0;
         }
-        return 1;
+        return;
     }
-    const int nv = N / 8, ppw = 64 / nv;
-    const long long groups = (p.M + ppw - 1) / ppw;
-    p.groups_per_wave = (int)((groups * samples + 16383) / 16384);
-    constexpr int U = 8;                                             // (8 pixels in flight per lane: 307 / 159 / 152 us against 321 / 171 / 158 with 4)
-    p.groups_per_wave = (p.groups_per_wave + U - 1) / U * U;         // (whole steps of U pixels in flight)
-    if (p.groups_per_wave < U) p.groups_per_wave = U;
-    if (p.groups_per_wave > 32) p.groups_per_wave = 32;
-    const long long blocks = (groups + 4ll * p.groups_per_wave - 1) / (4ll * p.groups_per_wave);
-    if (blocks >= (1ll << 31) || samples > 65535) return 0;
-    dim3 grid((unsigned)blocks, samples);
+    const int nv = q.N / 8, ppw = 64 / nv;                           // nv in {8, 16, 32, 64} (thin_mode)
+    dim3 grid((unsigned)thin_grid(q, false, &p.groups_per_wave), samples);
     static const int sload = msg_tunable("MSG_THIN_SLOAD", 1);
     // (N = 512 only: 314 -> 238 us on 6 -> 512 @256^2, B=16; with 4 pixels per wave -- N = 128 -- it measured SLOWER, 158 -> 198 us)
     if (sload && nv == 64 && p.M % ppw == 0 && (((uintptr_t)x) & 63u) == 0 && (p.x_bstride * 2) % 64 == 0) {
         switch (nv) {
-#define THIN_KS(NV_) case NV_: hipLaunchKernelGGL((conv_thin_k_sload_kernel<NV_>), grid, dim3(256), 0, s, xp, wp, yp, p); return 1
+#define THIN_KS(NV_) case NV_: hipLaunchKernelGGL((conv_thin_k_sload_kernel<NV_>), grid, dim3(256), 0, s, xp, wp, yp, p); return
             THIN_KS(8); THIN_KS(16); THIN_KS(32); THIN_KS(64);
 #undef THIN_KS
-            default: return 0;
         }
     }
     switch (nv) {
-#define THIN_K(NV_) case NV_: hipLaunchKernelGGL((conv_thin_k_kernel<NV_, U>), grid, dim3(256), 0, s, xp, wp, yp, p); break
+#define THIN_K(NV_) case NV_: hipLaunchKernelGGL((conv_thin_k_kernel<NV_, THIN_K_U>), grid, dim3(256), 0, s, xp, wp, yp, p); break
         THIN_K(8); THIN_K(16); THIN_K(32); THIN_K(64);
 #undef THIN_K
-        default: return 0;
     }
-    return 1;
 }
-

@@ -27,7 +27,7 @@
 // Accumulators: a wave tile is 128 pixels x 64 columns (4 x 2 blocks of 32 x 32, 128 registers), operands swapped so that a
 // lane owns a pixel and four consecutive channels (see conv_fprop_pp.hip's epilogue).  One workgroup of EIGHT waves per CU
 // (two per SIMD, <= 256 registers each), all 160 KiB of its LDS: 128 KiB activations + eight 4-KiB epilogue patches.
-#include "msg_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
@@ -183,40 +183,40 @@ __global__ __launch_bounds__(64 * UC_WAVES, 1) void conv_upconv_kernel(const bf1
     }
 }
 
-extern "C" int msg_conv2d_fprop_upconv_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
-                                                int stride, int pad, int in_up, int pixel_shuffle, long long w_batch_stride) {
+bool conv_upconv_eligible(const ConvProblem& q, const ActEpilogue* act, bool has_bias, ConvPlan* plan) {
     static const int enabled = msg_tunable("MSG_CONV_UPCONV", 1);
-    if (!enabled || !pixel_shuffle || w_batch_stride == 0 || kh != 1 || kw != 1 || stride != 1 || pad != 0 || in_up != 1)
-        return 0;
-    if (Cx != UC_K || Ck != UC_K || N % 256 || (N / 4) % 64 || IH != OH || IW != OW) return 0;
-    const long long hw = (long long)OH * OW;
+    if (q.dtype != MSG_BF16 || has_bias || conv_act_mode(act)) return false;
+    if (!enabled || !q.pixel_shuffle || !q.per_sample() || q.kh != 1 || q.kw != 1 || q.stride != 1 || q.pad != 0 || q.in_up != 1)
+        return false;
+    if (q.Cx != UC_K || q.Ck != UC_K || q.N % 256 || (q.N / 4) % 64 || q.IH != q.OH || q.IW != q.OW) return false;
+    const long long hw = (long long)q.OH * q.OW, m_tiles = (hw + UC_M - 1) / UC_M;
     // measured against the ping-pong kernel (batch 16): 128^2 maps 810 vs 905-950 us; 64^2 238 vs 221-239; 32^2 91 vs 62 --
     // the 8-wave workgroups need >= 128 pixel tiles per sample to keep every XCD on one weight set
-    if (hw < 16384 || hw >= (1ll << 30)) return 0;
-    if (((hw + UC_M - 1) / UC_M) * B < 256) return 0;
-    return 1;
+    if (hw < 16384 || hw >= (1ll << 30)) return false;
+    if (m_tiles * q.B < 256 || m_tiles * q.B >= (1ll << 31)) return false;
+    if (q.w_batch_stride < (long long)q.N * UC_K) return false;      // (weight sets that overlap: not this kernel's layout)
+    *plan = ConvPlan{CONV_UPCONV, UC_M, q.N, true};
+    return true;
 }
 
-// Called by msg_conv2d_fprop (conv_fprop.hip) in front of the tile kernels; returns 1 if it launched.
-extern "C" int msg_conv2d_fprop_upconv_try(const void* x, const void* w, const float* bias, void* y,
-                                           int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                           int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                           long long w_batch_stride, const ActEpilogue* act, void* stream) {
-    if (bias || (act && act->enabled)) return 0;
-    if (!msg_conv2d_fprop_upconv_eligible(B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, stride, pad, in_up, pixel_shuffle,
-                                          w_batch_stride))
-        return 0;
-    if ((long long)B * (((long long)OH * OW + UC_M - 1) / UC_M) >= (1ll << 31) || w_batch_stride < (long long)N * UC_K) return 0;
+// (the public query has no epilogue argument and no dtype: a plain bf16 launch)
+extern "C" int msg_conv2d_fprop_upconv_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
+                                                int stride, int pad, int in_up, int pixel_shuffle, long long w_batch_stride) {
+    const ConvProblem q{MSG_BF16, 0, B, IH, IW, Cx, Ck, OH, OW, N, N / 4, kh, kw, stride, pad, in_up, pixel_shuffle, w_batch_stride};
+    ConvPlan plan;
+    return conv_upconv_eligible(q, nullptr, false, &plan);
+}
+
+void conv_upconv_launch(const ConvProblem& q, const ConvPlan&, const void* x, const void* w, void* y, void* stream) {
     UpconvParams p{};
-    p.B = B; p.H = OH; p.W = OW; p.Cx = Cx; p.N = N; p.O = N / 4; p.ldy = ldy;
-    p.x_bstride = (long long)IH * IW * Cx;
-    p.w_bstride = w_batch_stride;
-    p.y_bstride = 4ll * OH * OW * ldy;
-    p.m_tiles = (int)(((long long)OH * OW + UC_M - 1) / UC_M);
+    p.B = q.B; p.H = q.OH; p.W = q.OW; p.Cx = q.Cx; p.N = q.N; p.O = q.N / 4; p.ldy = q.ldy;
+    p.x_bstride = q.x_bstride();
+    p.w_bstride = q.w_batch_stride;
+    p.y_bstride = q.y_bstride();
+    p.m_tiles = (int)(((long long)q.OH * q.OW + UC_M - 1) / UC_M);
     static const int xcd_order = msg_tunable("MSG_UPCONV_XCD", 1);                               // MSG_UPCONV_XCD=0: plain sample-major order (A/B)
-    p.xcd_samples = xcd_order && B % 8 == 0;
-    dim3 grid((unsigned)((long long)p.m_tiles * B));
+    p.xcd_samples = xcd_order && q.B % 8 == 0;
+    dim3 grid((unsigned)((long long)p.m_tiles * q.B));
     hipLaunchKernelGGL(conv_upconv_kernel, grid, dim3(64 * UC_WAVES), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w,
                        (bf16_t*)y, p);
-    return 1;
 }

@@ -22,7 +22,7 @@
 // the kernel); other maps take the generic incremental addressing.
 // pixel_shuffle = 1 is the weight gradient of the generator's 2x2 stride-2 transposed conv: tap (dy,dx) pairs
 // X[b,h,w,:] with GY[b, 2h+dy, 2w+dx, :].
-#include "msg_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
@@ -514,41 +514,29 @@ extern "C" int msg_wgrad_reduce_launch(const float* ws, float* gw, long long sla
     return MSG_CHECK_LAUNCH();
 }
 
-// conv_wgrad_row3.hip: returns 0 if the geometry is not its own, 1 if it planned / launched, a negative MSG_E* code on
-// error.  *need = workspace floats of the launch it would make (0: no split).  plan_only: no launch.
-extern "C" int msg_conv2d_wgrad_row3_try(const void* gy, const void* x, float* gw, int dtype,
-                                         int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy, int O, int ldgw,
-                                         int kh, int kw, int stride, int pad, int pixel_shuffle,
-                                         int per_sample, int k_chunks, int oi_major, float gain,
-                                         float* ws, long long ws_floats, int plan_only, long long* need, void* stream);
-
-static int wgrad_impl(const void* gy, const void* x, float* gw, int dtype,
-                      int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy, int O, int ldgw,
-                      int kh, int kw, int stride, int pad, int pixel_shuffle,
-                      int per_sample, int k_chunks, int oi_major, float gain,
-                      float* ws, long long ws_floats, int plan_only, long long* need, void* stream) {
+static int wgrad_impl(const WgradProblem& q, const void* gy, const void* x, float* gw, float* ws, long long ws_floats,
+                      int plan_only, long long* need, void* stream) {
+    const int dtype = q.dtype, split = q.split, B = q.B, IH = q.IH, IW = q.IW, Cx = q.Cx, I = q.I, OH = q.OH, OW = q.OW, ldgy = q.ldgy,
+              O = q.O, ldgw = q.ldgw, kh = q.kh, kw = q.kw, stride = q.stride, pixel_shuffle = q.pixel_shuffle,
+              per_sample = q.per_sample, k_chunks = q.k_chunks, oi_major = q.oi_major;
     *need = 0;
     if (B == 0) return MSG_OK;
     if (B < 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || O <= 0 || I <= 0 || kh <= 0 ||
         kw <= 0 || stride <= 0 || Cx <= 0 || ldgy <= 0 || ldgw < I || ldgw % 4 || k_chunks <= 0)
         return MSG_EINVAL;
     if (!plan_only && (!gy || !x || !gw)) return MSG_EINVAL;
-    const int split = dtype == MSG_F32_SPLIT ? 3 : 0;      // fp32 storage, bf16 MFMA products (msg_hip.h)
-    if (split) dtype = MSG_F32;
     if (dtype != MSG_F32 && dtype != MSG_BF16) return MSG_EUNSUPPORTED;
     const int esz = dtype == MSG_BF16 ? 2 : 4, vec = 16 / esz;
     if (Cx % vec || ldgy % vec) return MSG_EUNSUPPORTED;
     if (!plan_only && (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gw | (uintptr_t)ws) & 15u)) return MSG_EUNSUPPORTED;
     {
-        const int r3 = msg_conv2d_wgrad_row3_try(gy, x, gw, dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad,
-                                                 pixel_shuffle, per_sample, k_chunks, oi_major, gain, ws, ws_floats, plan_only,
-                                                 need, stream);
+        const int r3 = conv_wgrad_row3_try(q, gy, x, gw, ws, ws_floats, plan_only, need, stream);
         if (r3 < 0) return r3;
         if (r3) return MSG_OK;                     // kh x 3 'same' convs on wide maps: three taps per workgroup
     }
     WgradParams p{};
     p.B = B; p.IH = IH; p.IW = IW; p.Cx = Cx; p.I = I; p.OH = OH; p.OW = OW; p.ldgy = ldgy; p.O = O;
-    p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad; p.pixel_shuffle = pixel_shuffle;
+    p.kh = kh; p.kw = kw; p.stride = stride; p.pad = q.pad; p.pixel_shuffle = pixel_shuffle;
     p.per_sample = per_sample;
     p.chunks_per_sample = k_chunks;
     const int kp = dtype == MSG_BF16 ? 64 : 32;
@@ -639,7 +627,7 @@ static int wgrad_impl(const void* gy, const void* x, float* gw, int dtype,
     p.gw_zstride = oi_major ? (long long)O * I * kh * kw : (long long)O * kh * kw * ldgw;
     p.slab = (long long)O * kh * kw * ldgw;
     p.oi_major = oi_major;
-    p.gain = gain;
+    p.gain = q.gain;
     p.nz = (int)zs;
     static const int slice_tiles2 = msg_tunable("MSG_WGRAD_SLICE_TILES", 6);
     p.xcd_slices = (p.o_tiles * p.i_tiles <= slice_tiles2 && variant != 4 && (slice_tiles2 == 1 || zs % 8 == 0 || zs >= 64)) ||
@@ -671,12 +659,20 @@ static int wgrad_impl(const void* gy, const void* x, float* gw, int dtype,
     return msg_wgrad_reduce_launch(ws, gw, p.slab, n_out, (int)chunks_per_out, O, kh * kw, I, ldgw, oi_major, stream);
 }
 
+static WgradProblem wgrad_problem(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy, int O, int ldgw,
+                                  int kh, int kw, int stride, int pad, int pixel_shuffle, int per_sample, int k_chunks,
+                                  int oi_major, float gain) {
+    const int split = dtype == MSG_F32_SPLIT ? 3 : 0;      // fp32 storage, bf16 MFMA products (msg_hip.h)
+    return WgradProblem{split ? (int)MSG_F32 : dtype, split, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
+                        per_sample, k_chunks, oi_major, gain};
+}
+
 extern "C" long long msg_conv2d_wgrad_workspace(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy,
                                                 int O, int ldgw, int kh, int kw, int stride, int pad, int pixel_shuffle,
                                                 int per_sample, int k_chunks) {
     long long need = 0;
-    const int rc = wgrad_impl(nullptr, nullptr, nullptr, dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad,
-                              pixel_shuffle, per_sample, k_chunks, 0, 1.f, nullptr, 0, 1, &need, nullptr);
+    const int rc = wgrad_impl(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
+                                            per_sample, k_chunks, 0, 1.f), nullptr, nullptr, nullptr, nullptr, 0, 1, &need, nullptr);
     return rc == MSG_OK ? need : (long long)rc;
 }
 
@@ -686,6 +682,6 @@ extern "C" int msg_conv2d_wgrad(const void* gy, const void* x, float* gw, int dt
                                 int per_sample, int k_chunks, int oi_major, float gain,
                                 float* ws, long long ws_floats, void* stream) {
     long long need = 0;
-    return wgrad_impl(gy, x, gw, dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
-                      per_sample, k_chunks, oi_major, gain, ws, ws_floats, 0, &need, stream);
+    return wgrad_impl(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle, per_sample,
+                                    k_chunks, oi_major, gain), gy, x, gw, ws, ws_floats, 0, &need, stream);
 }

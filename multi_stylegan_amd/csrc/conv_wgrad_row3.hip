@@ -15,7 +15,7 @@
 // Same LDS image as conv_wgrad.hip ([pixel][128 channels], rows rotated by 64 B * (pixel & 3), ds_read_b64_tr_b16),
 // same buffer-load addressing (per-thread constant offset + wave-uniform SGPR cursor, out-of-range rows read zeros),
 // same fp32 epilogue (plain stores into GW[o][tap][i], or into the K-slice's slab when the sum is split: conv_wgrad.hip).
-#include "msg_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -336,16 +336,14 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
     }
 }
 
-extern "C" int msg_wgrad_reduce_launch(const float* ws, float* gw, long long slab, int n_out, int chunks, int O, int taps,
-                                       int I, int ldgw, int oi_major, void* stream);
-
 // Called by msg_conv2d_wgrad (conv_wgrad.hip) after its argument checks; returns 1 if the geometry is this file's (planned,
 // and launched unless plan_only), 0 if not, a negative MSG_E* code on error.  *need = workspace floats (0: no split).
-extern "C" int msg_conv2d_wgrad_row3_try(const void* gy, const void* x, float* gw, int dtype,
-                                         int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy, int O, int ldgw,
-                                         int kh, int kw, int stride, int pad, int pixel_shuffle,
-                                         int per_sample, int k_chunks, int oi_major, float gain,
-                                         float* ws, long long ws_floats, int plan_only, long long* need, void* stream) {
+int conv_wgrad_row3_try(const WgradProblem& q, const void* gy, const void* x, float* gw, float* ws, long long ws_floats,
+                        int plan_only, long long* need, void* stream) {
+    const int dtype = q.dtype, B = q.B, IH = q.IH, IW = q.IW, Cx = q.Cx, I = q.I, OH = q.OH, OW = q.OW, ldgy = q.ldgy, O = q.O,
+              ldgw = q.ldgw, kh = q.kh, kw = q.kw, stride = q.stride, pad = q.pad, pixel_shuffle = q.pixel_shuffle,
+              per_sample = q.per_sample, oi_major = q.oi_major;
+    int k_chunks = q.k_chunks;
     static const int enabled = msg_tunable("MSG_WGRAD_ROW3", 1);
     static const int w32_on = msg_tunable("MSG_WGRAD_ROW3_W32", 1);                         // MSG_WGRAD_ROW3_W32=0: 32-wide maps stay on conv_wgrad_kernel (A/B)
     const bool w32 = w32_on && OW == 32 && OH % 2 == 0;
@@ -365,7 +363,7 @@ extern "C" int msg_conv2d_wgrad_row3_try(const void* gy, const void* x, float* g
     p.o_tiles = (O + 127) / 128;
     p.i_tiles = (I + 127) / 128;
     p.oi_major = oi_major;
-    p.gain = gain;
+    p.gain = q.gain;
     p.gw_zstride = oi_major ? (long long)O * I * kh * 3 : (long long)O * kh * 3 * ldgw;
     p.slab = (long long)O * kh * 3 * ldgw;
     const long long steps_per_sample = w32 ? OH / 2 : (long long)OH * (OW / R3_KP);

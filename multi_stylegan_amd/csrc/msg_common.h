@@ -236,3 +236,8 @@ __device__ __forceinline__ void msg_dma16(msg_desc_t desc, unsigned lds_addr, in
 #pragma clang diagnostic pop
 
 #define MSG_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? MSG_OK : MSG_ELAUNCH)
+
+// bias_act.hip: the fixed-order second stage over partial sums another kernel left -- grad_bias[c] = sum over n_b rows of
+// part_b[.][C], *grad_nw = sum of n_n entries of part_n (called by conv_fprop.hip and pointwise_head.hip)
+extern "C" int msg_bias_act_reduce_launch(const float* part_b, float* grad_bias, int C, long long n_b, const float* part_n,
+                                          float* grad_nw, long long n_n, void* stream);

@@ -13,9 +13,6 @@
 // step; the sums go through per-workgroup partial rows and the fixed-order reduce of bias_act.hip (deterministic).
 #include "msg_common.h"
 
-extern "C" int msg_bias_act_reduce_launch(const float* part_b, float* grad_bias, int C, long long n_b, const float* part_n,
-                                          float* grad_nw, long long n_n, void* stream);
-
 struct HeadParams {
     long long npix, ppb;           // pixels, pixels per workgroup
     int C, lanes_c;

@@ -414,6 +414,70 @@ def test_kernel_plans_respect_the_31_bit_offset_limits():
         assert need > 0 and need % (c * 9 * c) == 0, (c, ohw, need)          # whole slabs of O x taps x ldgw floats
 
 
+def test_dispatch_answers_match_the_recorded_table():
+    """The host-side answers of the convolution family -- msg_conv2d_fprop_plan, msg_conv2d_fprop_act_backward_workspace,
+    msg_conv2d_fprop_upconv_eligible, msg_conv2d_fprop_thin_eligible, msg_conv2d_wgrad_workspace -- over the grid of
+    tools/gen_dispatch_table.py (the models' geometries at 256^2 and 512^2, shared and per-sample weights, batch 1 .. 33, and both
+    sides of every eligibility threshold), against tests/golden/dispatch_table.json: the answers recorded BEFORE the forward dispatch
+    became one selection function.  Equality on every row, except four classes where the recorded answer named a kernel the
+    launch never ran and the answer is now what launches (the launch itself is as it was):
+      * thin N (<= 8 output channels) with Ck / 32 outside the instantiated {2, 4, 6, 8, 12, 16}: THIN (eligible 1) -> REG (0);
+      * MSG_F32_SPLIT with a long K sweep: DMA -> REG (the split-bf16 kernel stages through registers whatever the K length);
+      * the up-convolution with per-sample weight sets closer than one set (stride < N * 512): eligible 1 -> 0;
+      * thin with per-sample weights and more than 65535 samples (grid.y): THIN -> DMA / PP / REG, whichever tile kernel takes it.
+    None of them is a geometry of the models: their thin layers have 128 / 512 channels, the Python layer asks the plan with the
+    storage code (never MSG_F32_SPLIT), per-sample weight images are dense and batches are tens of samples.  And the grid does hold
+    the models' geometries: every conv_fprop* / conv_wgrad label of the per-shape kernel tables of the benchmark has a row."""
+    from multi_stylegan_amd import _lib
+    from multi_stylegan_amd.build import build
+    from tools import gen_dispatch_table as grid
+    build(verbose=False)
+    lib = _lib.lib()
+    with open(os.path.join(GOLDEN, "dispatch_table.json")) as f:
+        table = json.load(f)
+    rows = {name: fn() for name, fn in grid.ROWS.items()}
+    for name, r in rows.items():                       # the recorded answers belong to exactly these rows
+        assert grid.digest(r) == table["digest"][name] and len(r) == len(table[name]), name
+    assert not grid.missing_profile_geometries([os.path.join(ROOT, "profiles", "r05_shape_table.txt"),
+                                                os.path.join(ROOT, "profiles", "r05_shape_table_regularised.txt")])
+    thin_kc = (2, 4, 6, 8, 12, 16)
+    model_channels = (8, 64, 128, 256, 384, 512, 768, 1024)
+    truthful = {"plan": 0, "thin_eligible": 0, "upconv_eligible": 0}
+    bad = []
+    for args, ans in zip(rows["plan"], table["plan"]):
+        plan, ws0, ws1 = ans if isinstance(ans, list) else (ans, 0, 0)
+        dtype, ck, n = args[0], args[5], args[8]
+        if plan == _lib.MSG_PLAN_THIN and n <= 8 and ck // 32 not in thin_kc:
+            assert ck not in model_channels
+            plan, truthful["plan"] = _lib.MSG_PLAN_REG, truthful["plan"] + 1
+        elif dtype == _lib.MSG_F32_SPLIT and plan == _lib.MSG_PLAN_DMA:
+            plan, truthful["plan"] = _lib.MSG_PLAN_REG, truthful["plan"] + 1
+        elif plan == _lib.MSG_PLAN_THIN and args[11] and args[1] > 65535:     # (4x4 maps, 512 or 64 channels: 8 K-steps or 1)
+            plan, truthful["plan"] = (_lib.MSG_PLAN_DMA if ck == 512 else _lib.MSG_PLAN_REG), truthful["plan"] + 1
+        got = (lib.msg_conv2d_fprop_plan(*args), lib.msg_conv2d_fprop_act_backward_workspace(*args, 0),
+               lib.msg_conv2d_fprop_act_backward_workspace(*args, 1))
+        if got != (plan, ws0, ws1):
+            bad.append(("plan", args, (plan, ws0, ws1), got))
+    for args, mode in zip(rows["thin_eligible"], table["thin_eligible"]):
+        if mode == 1 and args[4] // 32 not in thin_kc:
+            assert args[4] not in model_channels
+            mode, truthful["thin_eligible"] = 0, truthful["thin_eligible"] + 1
+        if lib.msg_conv2d_fprop_thin_eligible(*args) != mode:
+            bad.append(("thin_eligible", args, mode, lib.msg_conv2d_fprop_thin_eligible(*args)))
+    for args, ok in zip(rows["upconv_eligible"], table["upconv_eligible"]):
+        if ok == 1 and args[14] < args[7] * 512:
+            ok, truthful["upconv_eligible"] = 0, truthful["upconv_eligible"] + 1
+        if lib.msg_conv2d_fprop_upconv_eligible(*args) != ok:
+            bad.append(("upconv_eligible", args, ok, lib.msg_conv2d_fprop_upconv_eligible(*args)))
+    for args, need in zip(rows["wgrad_workspace"], table["wgrad_workspace"]):
+        if lib.msg_conv2d_wgrad_workspace(*args) != need:
+            bad.append(("wgrad_workspace", args, need, lib.msg_conv2d_wgrad_workspace(*args)))
+    assert not bad, (len(bad), bad[:10])
+    assert len(rows["plan"]) > 2500 and len(rows["wgrad_workspace"]) > 1400
+    # the exceptions are exactly the rows the four classes describe (thin-N + split + 65536-sample plans; thin queries; up-conv queries)
+    assert truthful == {"plan": 60 + 51 + 2, "thin_eligible": 20, "upconv_eligible": 2}, truthful
+
+
 def test_non_square_conv_geometry_is_refused():
     """EqualizedConv2d keeps the reference's (h, w) tuple arguments; a non-square stride / padding must raise instead
     of being computed with the first entry (round-1 advice)."""
