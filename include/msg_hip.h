@@ -547,6 +547,32 @@ int msg_flat_adam(float* param, const float* grad, float* exp_avg, float* exp_av
                   void* stream);
 int msg_flat_ema(float* ema, const float* param, long long n, float decay, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The data feed's batch prepare: raw camera counts -> normalised, flipped float frames.  Replaces, for a whole batch in one
+ * call, what the reference's dataset does per sample on the host in its DataLoader workers: dataset/tlfm_dataset.py:186-197
+ * (bright-field normalisation, GFP / RFP range normalisation, vertical flip), dataset/utils.py:4-23 (normalize_0_1) and
+ * the RandomHorizontalFlip of the default `transformations` (dataset/tlfm_dataset.py:24-25, applied at :163/:172/:181).
+ * raw    [B, C, T, H, W] unsigned 16-bit counts, contiguous; C = 1 (bright field), 2 (+ GFP) or 3 (+ RFP)
+ * hflip  [B] bytes, non-zero = mirror every frame of that sample left-right; NULL = no sample is mirrored
+ * out    [B, C, T, H, W] MSG_F32 or MSG_BF16, every element written
+ * vflip  non-zero = every frame upside down (the dataset's `flip`)
+ * channel 0: (x - min) / (max - min) with min / max over the (b, t) frame; a CONSTANT frame gives 0 / 0 = NaN in all of its
+ *            pixels, exactly as the reference's normalize_0_1 does;
+ * channel 1: min(max(x - lo1, 0) / div1, 1); channel 2 likewise with (lo2, div2) -- the divisor is the reference's gfp_max /
+ *            rfp_max itself, not a range.
+ * Counts are unsigned (65535 is 65535.f), subtract and divide are IEEE fp32 (correctly rounded divide, no reciprocal), so the
+ * MSG_F32 result equals the reference's CPU result bit for bit; MSG_BF16 is its round-to-nearest-even.  Flips are applied on
+ * the store side, which equals the reference's "flip, then normalise".
+ * ws     msg_tlfm_prepare_workspace(B, T) 32-bit words; needs no initialisation and carries nothing between calls (the
+ *        entry writes every word it reads).  Two launches, no synchronisation.
+ * MSG_EINVAL: a non-positive size, C > 3, any other dtype, NULL raw / out / ws.
+ * ------------------------------------------------------------------------- */
+long long msg_tlfm_prepare_workspace(int B, int T);
+int msg_tlfm_prepare(const unsigned short* raw, const unsigned char* hflip, void* out, int dtype,
+                     int B, int C, int T, int H, int W, int vflip,
+                     float lo1, float div1, float lo2, float div2,
+                     unsigned int* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

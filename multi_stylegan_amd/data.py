@@ -12,6 +12,9 @@ whenever the batch is pageable.  Here:
   earlier; the slot is recycled once the compute stream has passed the last kernel that read it.
 * ``SyntheticBatches`` draws the batches on the device itself (``torch.rand`` in the dataset's [0, 1] range,
   dataset/tlfm_dataset.py:187,191): what the benchmark and smoke runs use when there is no dataset.
+* ``prepare_tlfm_batch`` / ``TLFMDeviceFeed`` feed the real dataset (``tlfm_dataset.TFLMDatasetGAN(..., raw=True)``): the
+  camera's 16-bit counts cross the bus as they are (half the bytes of the reference's fp32 frames) and one streaming kernel
+  call per batch (csrc/tlfm_prepare.hip) does the normalisation and the flips the reference does per sample on the host.
 
 ``ModelWrapper.train`` / ``_gan_training`` put every host iterable behind a ``DevicePrefetcher`` themselves.
 """
@@ -20,6 +23,8 @@ import threading
 from typing import Any, Iterable, Iterator, Optional, Union
 
 import torch
+
+from . import _lib
 
 
 def _map(fn, batch):
@@ -223,11 +228,89 @@ class SyntheticBatches:
             yield torch.rand(self.shape, device=self.device, generator=self.generator) if self.fresh else self._resident
 
 
+def _prepare_tlfm_host(frames: torch.Tensor, hflip: Optional[torch.Tensor], vertical_flip: bool, gfp, rfp,
+                       out_dtype: torch.dtype) -> torch.Tensor:
+    """The host's one definition of the dataset's arithmetic (dataset/tlfm_dataset.py:186-197, dataset/utils.py:4-23) on a
+    batch ``[B, C, T, H, W]`` of counts (uint16) or of float frames a transformation has already touched."""
+    if frames.dtype == torch.uint16:
+        frames = torch.from_numpy(frames.numpy().astype("float32"))       # exact; 65535 stays 65535
+    x = frames.to(torch.float32)
+    out = torch.empty_like(x)
+    flat = x[:, 0].flatten(start_dim=2)                                   # [B, T, H * W]: min / max per frame
+    lo, hi = flat.min(dim=2, keepdim=True)[0], flat.max(dim=2, keepdim=True)[0]
+    out[:, 0] = ((flat - lo) / (hi - lo)).reshape(x[:, 0].shape)          # a constant frame: 0 / 0 = NaN, as the reference
+    for c, (low, div) in zip(range(1, x.shape[1]), (gfp, rfp)):
+        out[:, c] = ((x[:, c] - low).clamp(min=0.0) / div).clamp(max=1.0)
+    if hflip is not None:
+        mirrored = hflip.reshape(-1).to(torch.bool)
+        out[mirrored] = out[mirrored].flip(dims=(-1,))
+    if vertical_flip:
+        out = out.flip(dims=(-2,))
+    return out.to(out_dtype)
+
+
+def prepare_tlfm_batch(raw: torch.Tensor, hflip: Optional[torch.Tensor] = None, *, vertical_flip: bool = True,
+                       gfp=(150., 2200.), rfp=(20., 2000.), out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Raw camera counts ``[B, C, T, H, W]`` (``torch.uint16``; C = 1 bright field, 2 + GFP, 3 + RFP) and the per-sample
+    horizontal-flip flags ``[B]`` (``torch.uint8`` or None) -> the normalised, flipped frames of the reference's dataset
+    (dataset/tlfm_dataset.py:186-197) as ``out_dtype`` (float32 or bfloat16): bright field min-max normalised per frame, GFP /
+    RFP ``((x - min).clamp(min=0) / max).clamp(max=1)`` with ``gfp`` / ``rfp`` = (min, max), vertical flip when
+    ``vertical_flip``.  A constant bright-field frame is NaN, as in the reference.
+
+    Device tensors go through ``msg_tlfm_prepare`` (one call for the batch on the current stream, a fresh output tensor);
+    CPU tensors through a torch statement of the same arithmetic -- the float32 results are bit-identical."""
+    if raw.ndim != 5 or not 1 <= raw.shape[1] <= 3:
+        raise ValueError(f"expected [B, C <= 3, T, H, W] frames, got {tuple(raw.shape)}")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"out_dtype {out_dtype}: float32 or bfloat16")
+    if hflip is not None and hflip.numel() != raw.shape[0]:
+        raise ValueError(f"hflip holds {hflip.numel()} flags for {raw.shape[0]} samples")
+    if not raw.is_cuda:
+        return _prepare_tlfm_host(raw, hflip, vertical_flip, gfp, rfp, out_dtype)
+    if raw.dtype != torch.uint16:
+        raise ValueError(f"device batches are raw counts (torch.uint16), got {raw.dtype}")
+    dev = _lib.require_gpu(raw, hflip)
+    raw = raw.contiguous()
+    if hflip is not None:
+        hflip = hflip.reshape(-1).to(torch.uint8).contiguous()
+    B, C, T, H, W = raw.shape
+    out = torch.empty(raw.shape, dtype=out_dtype, device=dev)
+    if raw.numel() == 0:
+        return out
+    lib = _lib.lib()
+    with _lib.on_device(dev):
+        ws = _lib.scratch_ptr(lib.msg_tlfm_prepare_workspace(B, T), dev)
+        with _lib.kernel_clock.span(("tlfm_prepare", out_dtype), raw.numel() * (2.0 + out.element_size())):
+            _lib.check(lib.msg_tlfm_prepare(raw.data_ptr(), _lib.ptr(hflip), out.data_ptr(), _lib.dtype_code(out), B, C, T, H, W,
+                                            int(bool(vertical_flip)), float(gfp[0]), float(gfp[1]), float(rfp[0]),
+                                            float(rfp[1]), ws, _lib.stream_of(dev)), "msg_tlfm_prepare")
+    return out
+
+
+class TLFMDeviceFeed:
+    """``for batch in TLFMDeviceFeed(loader, device)``: ``loader`` yields the ``(frames, hflip)`` batches of
+    ``TFLMDatasetGAN(..., raw=True)`` (default-collated: uint16 ``[B, C, T, H, W]``, uint8 ``[B]``); they cross the bus as
+    counts through a ``DevicePrefetcher`` and each is normalised on the compute stream by ``prepare_tlfm_batch``
+    (``prepare_kwargs``: its keyword arguments).  A yielded batch is a fresh tensor: it stays valid for as long as the consumer
+    keeps it, and the prefetcher's slot behind it is reused as soon as the consumer asks for the next batch."""
+
+    def __init__(self, loader: Iterable, device: Union[str, torch.device] = "cuda", depth: int = 2, **prepare_kwargs):
+        self.feed = DevicePrefetcher(loader, device, depth)
+        self.prepare_kwargs = prepare_kwargs
+
+    def __len__(self) -> int:
+        return len(self.feed)
+
+    def __iter__(self) -> Iterator[torch.Tensor]:
+        for frames, hflip in self.feed:
+            yield prepare_tlfm_batch(frames, hflip, **self.prepare_kwargs)
+
+
 def prefetch(loader: Iterable, device: Union[str, torch.device], depth: int = 2,
              transfer_dtype: Optional[torch.dtype] = None) -> Iterable:
     """``loader`` behind a DevicePrefetcher when that helps (a GPU target and a loader that is not already one of this
     module's device-side feeds); otherwise the loader itself."""
     device = torch.device(device)
-    if device.type != "cuda" or isinstance(loader, (DevicePrefetcher, SyntheticBatches)):
+    if device.type != "cuda" or isinstance(loader, (DevicePrefetcher, SyntheticBatches, TLFMDeviceFeed)):
         return loader
     return DevicePrefetcher(loader, device, depth, transfer_dtype)
