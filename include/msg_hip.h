@@ -573,6 +573,27 @@ int msg_tlfm_prepare(const unsigned short* raw, const unsigned char* hflip, void
                      float lo1, float div1, float lo2, float div2,
                      unsigned int* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Sample output: a generated batch -> the 8-bit RGB pictures the reference writes through torchvision.utils.save_image, composed
+ * in one pass.  Replaces the repeat_interleave / zero-fill / cat / permute chains, the fp32 device-to-host copy and the host
+ * quantisation of multi_stylegan/misc.py:132-166 (Logger.save_prediction, called at model_wrapper.py:166-174),
+ * scripts/get_gan_samples.py:44-60 and scripts/gan_latent_space_interpolation.py:46-59.
+ * seq    [B, C, T, H, W] MSG_F32 or MSG_BF16 (widened to fp32 first), contiguous; C = 1 .. 3
+ * out    [B, C, H, T*W, 3] bytes, interleaved RGB, every byte written.  As [B, C] sheets of H x (T*W): a sequence's frames side
+ *        by side, save_image(nrow=T, padding=0).  As [B] pictures of (C*H) x (T*W): the channels stacked top to bottom, the
+ *        interpolation frame.  The same memory.
+ * tints  three bits per channel at bits 3c .. 3c+2: bit 0 = write the red byte, bit 1 green, bit 2 blue; a cleared bit writes
+ *        0.  The reference's colours: bright field 7, GFP 2, RFP 1 -> 7 | 2 << 3 | 1 << 6.
+ * q = (uint8) trunc(min(max(fl(fl(x * 255) + 0.5), 0), 255)) in fp32, multiply and add rounded separately (torchvision's
+ * save_image with normalize=False); NaN -> 0, +inf -> 255, -inf -> 0.
+ * W % 16 == 0 and 16-byte aligned bases: 16 pixels per lane, 16-byte loads and stores; anything else one pixel per lane with the
+ * same arithmetic.  One launch, no workspace.
+ * MSG_EINVAL: a non-positive size, C > 3, any other dtype, NULL seq / out, tint bits above bit 3C - 1, more pixels than the
+ * launch's block index can address.
+ * ------------------------------------------------------------------------- */
+int msg_sample_sheet(const void* seq, unsigned char* out, int dtype,
+                     int B, int C, int T, int H, int W, int tints, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

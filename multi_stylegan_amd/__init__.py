@@ -9,9 +9,13 @@ from .loss import PathLengthRegularization, TopK
 from .model_wrapper import Draws, ModelWrapper
 from .multi_stylegan_generator import Generator as MultiStyleGANGenerator
 from .u_net_2d_discriminator import Discriminator as MultiStyleGANDiscriminator
+from .samples import (SheetWriter, dump_samples, epoch_sample_dump, interpolation_frames, interpolation_latents, sample_sheets,
+                      save_prediction, write_png)
 from .tlfm_dataset import TFLMDatasetGAN, read_tiff
 from .validation_metrics import FID, FVD, IS
 
 __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper", "Draws", "PathLengthRegularization",
            "TopK", "AdaptiveDiscriminatorAugmentation", "AugmentationPipeline", "GeneratorSampler", "load_generator_ema", "split_sequences", "validation_samples",
-           "DevicePrefetcher", "SyntheticBatches", "TLFMDeviceFeed", "prepare_tlfm_batch", "TFLMDatasetGAN", "read_tiff", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters"]
+           "DevicePrefetcher", "SyntheticBatches", "TLFMDeviceFeed", "prepare_tlfm_batch", "TFLMDatasetGAN", "read_tiff",
+           "sample_sheets", "write_png", "SheetWriter", "save_prediction", "epoch_sample_dump", "dump_samples", "interpolation_latents",
+           "interpolation_frames", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters"]
