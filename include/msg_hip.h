@@ -594,6 +594,52 @@ int msg_tlfm_prepare(const unsigned short* raw, const unsigned char* hflip, void
 int msg_sample_sheet(const void* seq, unsigned char* out, int dtype,
                      int B, int C, int T, int H, int W, int tints, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The adversarial objectives of the step: two means over up to two prediction tensors in one streaming pass, and their
+ * gradient in one more.  Replaces the softplus / minimum, broadcast-multiply and mean chains (and their backward kernels) of
+ * multi_stylegan/loss.py:9-94 (Wasserstein discriminator, CutMix and generator losses), :97-196 (the non-saturating logistic
+ * ones) and :198-280 (the hinge ones):
+ *   out[0] = (1 / n_real) sum_i a_i  r(x_i)   over pred_real   (a generator loss is this side applied to fake predictions)
+ *   out[1] = (1 / n_fake) sum_i a'_i f(x_i)   over pred_fake
+ *   kind                   r(x)              f(x)               r'(x)                            f'(x)
+ *   MSG_GAN_LOGISTIC       softplus(-x)      softplus(x)        -sigmoid(-x)                     sigmoid(x)
+ *   MSG_GAN_WASSERSTEIN    -x                x                  -1                               1
+ *   MSG_GAN_HINGE          -min(0, x - 1)    -min(0, -x - 1)    -1 (x < 1), -1/2 (x == 1), 0     1 (x > -1), 1/2 (x == -1), 0
+ * (the half slope at the kink is torch.minimum's at a tie; a NaN prediction gives a NaN loss, as torch.minimum does; softplus
+ * is torch's: z for z > 20, log1p(exp(z)) otherwise.)
+ *   aux_mode
+ *   MSG_GAN_AUX_NONE     a = a' = 1; aux = NULL
+ *   MSG_GAN_AUX_WEIGHT   a_i = a'_i = aux[i mod P], aux [P] fp32: the reference's weight.view(1, 1, 1, H, W) broadcast over
+ *                        predictions whose last two dimensions are H x W, P = H W (P need not divide n)
+ *   MSG_GAN_AUX_LABEL    CutMix: a_i = aux[i], a'_i = 1 - aux[i], aux [n_real] fp32, and BOTH sides read pred_real
+ *                        (n_fake == n_real; pred_fake NULL or pred_real itself)
+ * pred_real / pred_fake  n_real / n_fake elements, MSG_F32 or MSG_BF16 (widened to fp32; sums and results are fp32), contiguous,
+ *                        any alignment (16-byte aligned tensors are read 16 bytes per lane and load).  The counts may differ.
+ *                        A side with n = 0 and a NULL pointer is absent and its out is 0; both absent is MSG_EINVAL.
+ * out    [2] fp32, both written.
+ * ws     msg_gan_loss_workspace(n_real, n_fake) fp32 words (0 for small inputs: ws may then be NULL); needs no initialisation
+ *        and carries nothing between calls.  ws_floats: what the caller allocated.
+ * Bit-identical from run to run: no atomics; the grid and the summation order follow from the element counts alone (not from
+ * dtype or alignment): one launch writes per-workgroup partial sums, a second, one workgroup per side, adds them in a fixed
+ * order; a single launch where one workgroup per side suffices.
+ *
+ * msg_gan_loss_backward: grad_real[i] = ((grad_out[0] / n_real) a_i) r'(x_i), grad_fake[i] = ((grad_out[1] / n_fake) a'_i)
+ * f'(x_i), in the predictions' dtype (bf16: round to nearest even); MSG_GAN_AUX_LABEL: grad_real[i] is the sum of the two and
+ * grad_fake must be NULL.  grad_out [2] fp32 is read on the device.  A NULL grad_real / grad_fake (not both) skips that side.
+ * A zero slope or a zero label gives an exact zero.  One launch, no workspace.
+ * MSG_EINVAL: any other dtype, kind or aux_mode, a negative count, a count without its pointer, aux against its mode, P <= 0
+ * with a weight map, a workspace that is NULL or too small where one is needed.
+ * ------------------------------------------------------------------------- */
+enum { MSG_GAN_LOGISTIC = 0, MSG_GAN_WASSERSTEIN = 1, MSG_GAN_HINGE = 2 };
+enum { MSG_GAN_AUX_NONE = 0, MSG_GAN_AUX_WEIGHT = 1, MSG_GAN_AUX_LABEL = 2 };
+long long msg_gan_loss_workspace(long long n_real, long long n_fake);
+int msg_gan_loss(const void* pred_real, const void* pred_fake, const float* aux, float* out, int dtype, int kind,
+                 int aux_mode, long long n_real, long long n_fake, long long P, float* ws, long long ws_floats,
+                 void* stream);
+int msg_gan_loss_backward(const void* pred_real, const void* pred_fake, const float* aux, const float* grad_out,
+                          void* grad_real, void* grad_fake, int dtype, int kind, int aux_mode,
+                          long long n_real, long long n_fake, long long P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

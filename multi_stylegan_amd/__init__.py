@@ -5,7 +5,9 @@ from .config import (generation_hyperparameters, multi_style_gan_generator_confi
                      u_net_2d_discriminator_config)
 from .data import DevicePrefetcher, SyntheticBatches, TLFMDeviceFeed, prepare_tlfm_batch
 from .inference import GeneratorSampler, load_generator_ema, split_sequences, validation_samples
-from .loss import PathLengthRegularization, TopK
+from .loss import (HingeDiscriminatorLoss, HingeDiscriminatorLossCutMix, HingeGeneratorLoss, PathLengthRegularization,
+                   R2Regularization, TopK, WassersteinDiscriminatorLoss, WassersteinDiscriminatorLossCutMix,
+                   WassersteinGeneratorLoss)
 from .model_wrapper import Draws, ModelWrapper
 from .multi_stylegan_generator import Generator as MultiStyleGANGenerator
 from .u_net_2d_discriminator import Discriminator as MultiStyleGANDiscriminator
@@ -18,4 +20,6 @@ __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper
            "TopK", "AdaptiveDiscriminatorAugmentation", "AugmentationPipeline", "GeneratorSampler", "load_generator_ema", "split_sequences", "validation_samples",
            "DevicePrefetcher", "SyntheticBatches", "TLFMDeviceFeed", "prepare_tlfm_batch", "TFLMDatasetGAN", "read_tiff",
            "sample_sheets", "write_png", "SheetWriter", "save_prediction", "epoch_sample_dump", "dump_samples", "interpolation_latents",
-           "interpolation_frames", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters"]
+           "interpolation_frames", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters",
+           "WassersteinDiscriminatorLoss", "WassersteinDiscriminatorLossCutMix", "WassersteinGeneratorLoss", "HingeGeneratorLoss",
+           "HingeDiscriminatorLoss", "HingeDiscriminatorLossCutMix", "R2Regularization"]
