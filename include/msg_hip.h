@@ -523,6 +523,30 @@ enum {
 };
 int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
                           int kh, int kw, long long w_batch_stride);
+/* What msg_conv2d_wgrad launches for a problem (no launch): the arguments of msg_conv2d_wgrad_workspace, and `out` receives the
+ * first min(n_out_fields, MSG_WPLAN_FIELDS) of
+ *   [0] kernel          a MSG_WPLAN_* code
+ *   [1] nz              K-slices in the grid
+ *   [2] chunks_per_out  K-slices that add up to one result (> 1: slabs in the workspace + the fixed-order sum)
+ *   [3] n_out           results: B with per-sample weights, else 1
+ *   [4] slice_pixels    logical pixels of one K-slice
+ *   [5] OWv  [6] OHv    logical row width / row count of the K loop (OW x OH, or rows padded to a power of two)
+ *   [7] fold            1: the batch is folded into K     [8] xcd_slices  1: one K-slice per XCD
+ *   [9] blocks          workgroups of the contraction kernel
+ *   [10] need           what msg_conv2d_wgrad_workspace returns
+ * Returns MSG_OK, or the MSG_E* code msg_conv2d_wgrad returns for the geometry before it looks at a pointer (`out` is then left
+ * alone).  B = 0: MSG_OK and all fields 0.  For tests and timing labels. */
+enum {
+    MSG_WPLAN_GENERIC = 0,  /* 128x128 tile of one tap, incremental addressing */
+    MSG_WPLAN_DMA = 1,      /* ... LDS-DMA staging (tuning builds only: MSG_CONV_VARIANT=1) */
+    MSG_WPLAN_UNI = 2,      /* ... uniform-row addressing (buffer loads; power-of-two or padded rows) */
+    MSG_WPLAN_ROW3 = 3,     /* kh x 3 row-sharing kernel, maps a multiple of 64 wide */
+    MSG_WPLAN_ROW3_W32 = 4, /* kh x 3 row-sharing kernel, maps exactly 32 wide */
+    MSG_WPLAN_FIELDS = 11
+};
+int msg_conv2d_wgrad_plan(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy,
+                          int O, int ldgw, int kh, int kw, int stride, int pad, int pixel_shuffle,
+                          int per_sample, int k_chunks, long long* out, int n_out_fields);
 /* 1 if msg_conv2d_fprop takes this problem to the activation-stationary sub-pixel up-convolution kernel (conv_upconv.hip:
  * K = 512, N = 4 * 512, per-sample weights, pixel-shuffled output, bf16), else 0.  For timing labels. */
 int msg_conv2d_fprop_upconv_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,

@@ -536,6 +536,20 @@ def _grad_dest(param):
     return grad_destination(param)
 
 
+def wgrad_k_chunks(b, o, i, taps, oh, ow, per_sample, kp):
+    """The K split _launch_wgrad asks msg_conv2d_wgrad for (kp: pixels per K-step, 64 bf16 / 32 fp32)."""
+    tiles = ((o + 127) // 128) * ((i + 127) // 128) * taps * b
+    if per_sample:
+        # one K sweep per (sample, tile, tap) unless that leaves most of the chip idle (the 512 -> 3 toRGB layers: 64
+        # workgroups); then the pixels are split into K-slices
+        return max(1, min((oh * ow) // (16 * kp), 1024 // tiles)) if tiles < 256 else 1
+    # (shared weights: the library folds the batch into K and picks the slice count; k_chunks only matters where it cannot)
+    k_chunks = max(1, min((oh * ow + 4 * kp - 1) // (4 * kp), (1024 + tiles - 1) // tiles))
+    while b * k_chunks > 65535:
+        k_chunks -= 1
+    return k_chunks
+
+
 def _launch_wgrad(gy, x, o, i, kh, kw, stride, pad, pixel_shuffle, per_sample, low_hw, raw=False, gain=1.0, out=None,
                   mode=None):
     """out: a contiguous fp32 tensor of o*i*kh*kw elements (the parameter's own layout) that receives a SHARED gradient."""
@@ -546,18 +560,7 @@ def _launch_wgrad(gy, x, o, i, kh, kw, stride, pad, pixel_shuffle, per_sample, l
     oh, ow = low_hw if pixel_shuffle else gv.shape[2:]
     taps = kh * kw
     ldgw = _round_up(i, 4)
-    kp = 64 if x.dtype == torch.bfloat16 else 32
-    if per_sample:
-        # one K sweep per (sample, tile, tap) unless that leaves most of the chip idle (the 512 -> 3 toRGB layers: 64
-        # workgroups); then the pixels are split into K-slices
-        tiles = ((o + 127) // 128) * ((i + 127) // 128) * taps * b
-        k_chunks = max(1, min((oh * ow) // (16 * kp), 1024 // tiles)) if tiles < 256 else 1
-    else:
-        # (shared weights: the library folds the batch into K and picks the slice count; k_chunks only matters where it cannot)
-        tiles = ((o + 127) // 128) * ((i + 127) // 128) * taps * b
-        k_chunks = max(1, min((oh * ow + 4 * kp - 1) // (4 * kp), (1024 + tiles - 1) // tiles))
-        while b * k_chunks > 65535:
-            k_chunks -= 1
+    k_chunks = wgrad_k_chunks(b, o, i, taps, oh, ow, per_sample, 64 if x.dtype == torch.bfloat16 else 32)
     geom = (_contraction_code(x, mode), b, ih, iw, cx, i, oh, ow, ldgy, o, ldgw, kh, kw, stride, pad, int(pixel_shuffle),
             int(per_sample), k_chunks)
     # K-slices that add up to one result meet in a workspace of per-slice slabs and a fixed-order sum (deterministic; no

@@ -8,7 +8,11 @@
 // that kernel's conditions (it fills the plan when it says yes) and `void conv_<k>_launch(problem, plan, pointers, stream)`, which
 // cannot decline.  Everything that asks "what would run" -- msg_conv2d_fprop_plan, the sign-byte gate, the activation-backward
 // workspace -- asks conv_fprop_select, i.e. the code the launch goes through.
-// Weight gradients (msg_conv2d_wgrad*): wgrad_impl / conv_wgrad_row3_try plan and launch through the same code (plan_only).
+// Weight gradients (msg_conv2d_wgrad*): the same shape.  conv_wgrad_select (conv_wgrad.hip) is the only place that knows the order
+// row3, generic; a WgradPlan is a value -- kernel, K split, logical rows, grid, workspace -- that the launch, the workspace query and
+// msg_conv2d_wgrad_plan all take from it.  `conv_wgrad_<k>_eligible(problem, WgradPlan*)` holds all of a kernel's conditions and
+// fills the plan; `conv_wgrad_<k>_launch(problem, plan, pointers, stream)` fills the kernel's parameter struct from the two and
+// cannot decline.  Both files take their K split from conv_wgrad_ksplit below.
 #pragma once
 #include "msg_common.h"
 
@@ -85,18 +89,51 @@ void conv_pp_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, c
 
 // ---- weight gradients
 struct WgradProblem {
-    int dtype;                      // MSG_F32 or MSG_BF16 (MSG_F32_SPLIT: MSG_F32 with split = 3)
-    int split;
+    int dtype, split;               // MSG_F32 or MSG_BF16 (MSG_F32_SPLIT: MSG_F32 with split = 3)
     int B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw;
     int kh, kw, stride, pad, pixel_shuffle;
     int per_sample, k_chunks, oi_major;
     float gain;
+    int esz() const { return dtype == MSG_BF16 ? 2 : 4; }
+    long long gy_bytes() const { return (long long)(pixel_shuffle ? 4 : 1) * OH * OW * ldgy * esz(); }   // of one sample
+    long long x_bytes() const { return (long long)IH * IW * Cx * esz(); }
+    long long slab() const { return (long long)O * kh * kw * ldgw; }                      // floats of one result in the kernel layout
+    long long gw_zstride() const { return oi_major ? (long long)O * I * kh * kw : slab(); }
 };
 
-// conv_wgrad_row3.hip: 0 if the geometry is not its own, 1 if it planned (and launched, unless plan_only), a negative MSG_E* code
-// on error.  *need = workspace floats of the launch it would make (0: no split).
-int conv_wgrad_row3_try(const WgradProblem& q, const void* gy, const void* x, float* gw, float* ws, long long ws_floats,
-                        int plan_only, long long* need, void* stream);
-// conv_wgrad.hip: the reduce for `n_out` results of `chunks` slabs each
-extern "C" int msg_wgrad_reduce_launch(const float* ws, float* gw, long long slab, int n_out, int chunks, int O, int taps,
-                                       int I, int ldgw, int oi_major, void* stream);
+enum WgradKernel {                  // (the values are the MSG_WPLAN_* codes of msg_hip.h)
+    WGRAD_GENERIC, WGRAD_DMA, WGRAD_UNI,    // conv_wgrad.hip: 128 x 128 tile of one tap; incremental addressing / LDS-DMA staging (A/B) / uniform rows
+    WGRAD_ROW3, WGRAD_ROW3_W32              // conv_wgrad_row3.hip: the three horizontal taps in one workgroup; maps of 64 k / exactly 32 columns
+};
+
+struct WgradPlan {                  // (value-initialised: the plan of an empty batch -- nothing to launch, no workspace)
+    WgradKernel kernel;
+    int nz, slice_pixels;           // K-slices in the grid, and the logical pixels of one
+    int chunks_per_out, n_out;      // K-slices that add up to one result (> 1: slabs + the fixed-order reduce), and results
+    int OWv, OHv;                   // logical row width / row count of the K loop (WgradParams)
+    int fold, xcd_slices;           // the batch is folded into K; one K-slice per XCD
+    long long blocks, need;         // workgroups of the contraction kernel; workspace floats (0: no split)
+    bool supported;                 // false: the generic kernel's own grid limits: MSG_EUNSUPPORTED
+};
+
+// The K split both files use: the chunk count c in 1 .. max_chunks that minimises (rounds of `round_wgs` co-resident workgroups) x
+// (K-steps per workgroup + fixed_steps + slab_steps when the sum is split); the first minimum wins, and no count beyond the first with
+// more than max_wgs workgroups is tried.  by8: only 1, 8, 16, ... (K-slices dealt to the XCDs eight at a time).  wgs: per chunk.
+struct WgradSplitModel { int round_wgs, fixed_steps, slab_steps; long long max_chunks, max_wgs; bool by8; };
+inline long long conv_wgrad_ksplit(long long steps, long long wgs, const WgradSplitModel& m) {
+    long long chunks = 1, best = -1;
+    for (long long c = 1; c <= m.max_chunks; c += (m.by8 && c >= 8 ? 8 : 1)) {
+        if (m.by8 && c > 1 && c < 8) continue;
+        const long long rounds = (wgs * c + m.round_wgs - 1) / m.round_wgs;
+        const long long cost = rounds * ((steps + c - 1) / c + m.fixed_steps + (c > 1 ? m.slab_steps : 0));
+        if (best < 0 || cost < best) { best = cost; chunks = c; }
+        if (wgs * c > m.max_wgs) break;
+    }
+    return chunks;
+}
+
+WgradPlan conv_wgrad_select(const WgradProblem& q);
+// conv_wgrad_row3.hip
+bool conv_wgrad_row3_eligible(const WgradProblem& q, WgradPlan* plan);
+void conv_wgrad_row3_launch(const WgradProblem& q, const WgradPlan& plan, const void* gy, const void* x, float* gw, float* ws,
+                            void* stream);

@@ -503,54 +503,32 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
         if (i + k < I) dst[(long long)k * taps] = e[k];
 }
 
-// Launches the reduce for `n_out` results of `chunks` slabs each (shared by conv_wgrad_row3.hip).
-extern "C" int msg_wgrad_reduce_launch(const float* ws, float* gw, long long slab, int n_out, int chunks, int O, int taps,
-                                       int I, int ldgw, int oi_major, void* stream) {
-    const long long nvec = slab >> 2;
-    const long long blocks = (nvec + 63) / 64;
-    if (blocks >= (1ll << 31) || n_out > 65535) return MSG_EUNSUPPORTED;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks, (unsigned)n_out), dim3(256), 0, (hipStream_t)stream,
-                       ws, gw, slab, chunks, O, taps, I, ldgw, oi_major);
+// Launches the reduce of a split plan: n_out results of chunks_per_out slabs each.
+static int wgrad_reduce_launch(const WgradProblem& q, const WgradPlan& plan, const float* ws, float* gw, void* stream) {
+    const long long blocks = ((q.slab() >> 2) + 63) / 64;
+    if (blocks >= (1ll << 31) || plan.n_out > 65535) return MSG_EUNSUPPORTED;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks, (unsigned)plan.n_out), dim3(256), 0, (hipStream_t)stream,
+                       ws, gw, q.slab(), plan.chunks_per_out, q.O, q.kh * q.kw, q.I, q.ldgw, q.oi_major);
     return MSG_CHECK_LAUNCH();
 }
 
-static int wgrad_impl(const WgradProblem& q, const void* gy, const void* x, float* gw, float* ws, long long ws_floats,
-                      int plan_only, long long* need, void* stream) {
-    const int dtype = q.dtype, split = q.split, B = q.B, IH = q.IH, IW = q.IW, Cx = q.Cx, I = q.I, OH = q.OH, OW = q.OW, ldgy = q.ldgy,
-              O = q.O, ldgw = q.ldgw, kh = q.kh, kw = q.kw, stride = q.stride, pixel_shuffle = q.pixel_shuffle,
-              per_sample = q.per_sample, k_chunks = q.k_chunks, oi_major = q.oi_major;
-    *need = 0;
-    if (B == 0) return MSG_OK;
-    if (B < 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || O <= 0 || I <= 0 || kh <= 0 ||
-        kw <= 0 || stride <= 0 || Cx <= 0 || ldgy <= 0 || ldgw < I || ldgw % 4 || k_chunks <= 0)
-        return MSG_EINVAL;
-    if (!plan_only && (!gy || !x || !gw)) return MSG_EINVAL;
-    if (dtype != MSG_F32 && dtype != MSG_BF16) return MSG_EUNSUPPORTED;
-    const int esz = dtype == MSG_BF16 ? 2 : 4, vec = 16 / esz;
-    if (Cx % vec || ldgy % vec) return MSG_EUNSUPPORTED;
-    if (!plan_only && (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gw | (uintptr_t)ws) & 15u)) return MSG_EUNSUPPORTED;
-    {
-        const int r3 = conv_wgrad_row3_try(q, gy, x, gw, ws, ws_floats, plan_only, need, stream);
-        if (r3 < 0) return r3;
-        if (r3) return MSG_OK;                     // kh x 3 'same' convs on wide maps: three taps per workgroup
-    }
-    WgradParams p{};
-    p.B = B; p.IH = IH; p.IW = IW; p.Cx = Cx; p.I = I; p.OH = OH; p.OW = OW; p.ldgy = ldgy; p.O = O;
-    p.kh = kh; p.kw = kw; p.stride = stride; p.pad = q.pad; p.pixel_shuffle = pixel_shuffle;
-    p.per_sample = per_sample;
-    p.chunks_per_sample = k_chunks;
-    const int kp = dtype == MSG_BF16 ? 64 : 32;
+// The 128 x 128 kernel takes every problem: the plan it fills is unsupported only beyond its grid limits.
+static bool conv_wgrad_generic_eligible(const WgradProblem& q, WgradPlan* plan) {
+    static const int variant = msg_tunable("MSG_CONV_VARIANT", 0);          // A/B switches: 1 LDS-DMA staging, 2 generic addressing, 3 no folding, 4 / 5 slice order
+    static const int pad_rows = msg_tunable("MSG_WGRAD_PAD_ROWS", 1);
+    static const int target_wgs = msg_tunable("MSG_WGRAD_TARGET_WGS", 0);   // MSG_WGRAD_TARGET_WGS > 0: the old fixed-target rule (A/B)
+    static const int slice_tiles = msg_tunable("MSG_WGRAD_SLICE_TILES", 6); // MSG_WGRAD_SLICE_TILES: largest channel-tile count that takes the slice-per-XCD order
+    static const int slab_cost = msg_tunable("MSG_WGRAD_SLAB_COST", 6);
+    const int B = q.B, OH = q.OH, OW = q.OW, taps = q.kh * q.kw, kp = q.dtype == MSG_BF16 ? 64 : 32;
+    const long long gy_bytes = q.gy_bytes(), x_bytes = q.x_bytes();
+    const long long tiles = (long long)((q.O + WT - 1) / WT) * ((q.I + WT - 1) / WT);
     // uniform-row addressing: K-steps map onto whole rows / whole row fragments and per-sample tensors fit 31-bit offsets.
     // Maps one or a few columns short of a power of two -- the discriminator's stride-2 convolutions give 127, 63, 31 -- take it
     // too, on rows padded to that power of two: the K loop runs over OH x OWv logical pixels, the padding columns read zeros
     // (<= 1/16 of the MFMA work), and the ~170 vector instructions per K-step of the generic incremental addressing are gone
     // (these weight gradients ran at 480-490 TFLOP/s; MSG_WGRAD_PAD_ROWS=0: off).
-    static const int variant = msg_tunable("MSG_CONV_VARIANT", 0);
-    static const int pad_rows = msg_tunable("MSG_WGRAD_PAD_ROWS", 1);
-    const long long gy_bytes = (long long)(pixel_shuffle ? 4 : 1) * OH * OW * ldgy * esz;
-    const long long x_bytes = (long long)IH * IW * Cx * esz;
     int owv = OW, ohv = OH;
-    if (pad_rows && !pixel_shuffle && !(kp % OW == 0 || OW % kp == 0)) {
+    if (pad_rows && !q.pixel_shuffle && !(kp % OW == 0 || OW % kp == 0)) {
         int v = 1;
         while (v < OW) v <<= 1;
         if ((long long)v * 15 <= (long long)OW * 16) {
@@ -559,7 +537,7 @@ static int wgrad_impl(const WgradProblem& q, const void* gy, const void* x, floa
             if (v < kp && (OH * v) % kp) ohv = ((OH * v + kp - 1) / kp * kp) / v;
         }
     }
-    const bool can_fold0 = !per_sample && variant != 3;
+    const bool can_fold0 = !q.per_sample && variant != 3;
     auto uni_ok = [&](int wl) {
         const long long np = (long long)(wl == OW ? OH : ohv) * wl;
         bool u = variant != 2 && variant != 1 && (kp % wl == 0 || wl % kp == 0) && gy_bytes < (1ll << 31) && x_bytes < (1ll << 31);
@@ -575,78 +553,64 @@ static int wgrad_impl(const WgradProblem& q, const void* gy, const void* x, floa
     bool uni = uni_ok(owv);
     if (!uni && owv != OW) { owv = OW; uni = uni_ok(OW); }        // (padding did not buy uniform rows: the map as it is)
     if (owv == OW) ohv = OH;
-    p.OWv = owv;
-    p.OHv = ohv;
     const int npix = ohv * owv;                                    // logical pixels per sample
-    p.pix_per_chunk = (((npix + k_chunks - 1) / k_chunks + kp - 1) / kp) * kp;
-    long long zs = (long long)B * k_chunks;
-    const bool can_fold = can_fold0 && (long long)B * npix < (1ll << 31);
+    int slice_pixels = (((npix + q.k_chunks - 1) / q.k_chunks + kp - 1) / kp) * kp;
+    long long zs = (long long)B * q.k_chunks;
+    const bool fold = can_fold0 && (long long)B * npix < (1ll << 31);
     // shared weights: fold the batch into K (one sweep over the concatenated pixels of all samples), so that small maps
     // still give every workgroup a long K loop and the slabs to add shrink from B*chunks to `chunks` per element
-    if (can_fold) {
+    if (fold) {
         const long long steps = ((long long)B * npix + kp - 1) / kp;
-        const long long tiles = (long long)((O + WT - 1) / WT) * ((I + WT - 1) / WT) * kh * kw;
-        // K split: pick the chunk count that minimises (rounds of 512 co-resident workgroups) x (K-steps per workgroup +
-        // a fixed prologue/epilogue cost of ~8 steps, + ~MSG_WGRAD_SLAB_COST steps when the sum is split: a workgroup's
-        // 64-KiB slab tile is written once and read once by the reduce).  A fixed target count left a quarter of the chip
-        // idle in the last round on some layers (768->768 @32^2: 5 chunks = 3.2 rounds, 274 us; 3 chunks = 1.9 rounds, 226 us).
-        static const int target_wgs = msg_tunable("MSG_WGRAD_TARGET_WGS", 0);                      // MSG_WGRAD_TARGET_WGS > 0: the old fixed-target rule (A/B)
-        static const int slice_tiles = msg_tunable("MSG_WGRAD_SLICE_TILES", 6);                     // MSG_WGRAD_SLICE_TILES: largest channel-tile count that takes the slice-per-XCD order
-        static const int slab_cost = msg_tunable("MSG_WGRAD_SLAB_COST", 6);
-        const bool sliced = tiles <= (long long)kh * kw * slice_tiles;       // slices are dealt to the XCDs 8 at a time
-        long long chunks = 1;
+        // K split: rounds of 512 co-resident workgroups, ~8 steps of prologue / epilogue, ~MSG_WGRAD_SLAB_COST steps when the sum is
+        // split (a workgroup's 64-KiB slab tile is written once and read once by the reduce).  A fixed target count left a quarter of
+        // the chip idle in the last round on some layers (768->768 @32^2: 5 chunks = 3.2 rounds, 274 us; 3 chunks = 1.9 rounds, 226 us).
+        const bool sliced = tiles <= slice_tiles;                  // slices are dealt to the XCDs 8 at a time
+        long long chunks;
         if (target_wgs > 0) {
-            chunks = (target_wgs + tiles - 1) / tiles;
+            chunks = (target_wgs + tiles * taps - 1) / (tiles * taps);
             if (chunks > steps / 4) chunks = steps / 4;
             if (sliced && chunks >= 8) chunks &= ~7ll;
+            if (chunks < 1) chunks = 1;
         } else {
-            long long best = -1;
-            const long long cmax = steps / 4 < 4096 ? steps / 4 : 4096;
-            for (long long c = 1; c <= cmax; c += (sliced && c >= 8 ? 8 : 1)) {
-                if (sliced && c > 1 && c < 8) continue;
-                const long long rounds = (tiles * c + 511) / 512;
-                const long long cost = rounds * ((steps + c - 1) / c + 8 + (c > 1 ? slab_cost : 0));
-                if (best < 0 || cost < best) { best = cost; chunks = c; }
-                if (tiles * c > 8192) break;
-            }
+            chunks = conv_wgrad_ksplit(steps, tiles * taps, {512, 8, slab_cost, steps / 4 < 4096 ? steps / 4 : 4096, 8192, sliced});
         }
-        if (chunks < 1) chunks = 1;
         if (chunks > 65535) chunks = 65535;
-        p.fold = 1;
-        p.pix_per_chunk = (int)(((steps + chunks - 1) / chunks) * kp);
-        zs = ((long long)B * npix + p.pix_per_chunk - 1) / p.pix_per_chunk;
-        p.chunks_per_sample = (int)zs;                   // (z = chunk; the sample index derived from it is always 0)
+        slice_pixels = (int)(((steps + chunks - 1) / chunks) * kp);
+        zs = ((long long)B * npix + slice_pixels - 1) / slice_pixels;   // (z = chunk; the sample index derived from it is always 0)
     }
     // K-slices per result: a result that is the sum of several slices goes through slabs + the fixed-order reduce
-    const long long chunks_per_out = per_sample ? k_chunks : zs;
-    const int n_out = per_sample ? B : 1;
-    p.split = chunks_per_out > 1;
-    p.o_tiles = (O + WT - 1) / WT;
-    p.i_tiles = (I + WT - 1) / WT;
-    p.ldgw = ldgw;
-    p.gw_zstride = oi_major ? (long long)O * I * kh * kw : (long long)O * kh * kw * ldgw;
-    p.slab = (long long)O * kh * kw * ldgw;
-    p.oi_major = oi_major;
-    p.gain = q.gain;
-    p.nz = (int)zs;
-    static const int slice_tiles2 = msg_tunable("MSG_WGRAD_SLICE_TILES", 6);
-    p.xcd_slices = (p.o_tiles * p.i_tiles <= slice_tiles2 && variant != 4 && (slice_tiles2 == 1 || zs % 8 == 0 || zs >= 64)) ||
-                   (variant == 5 && zs % 8 == 0);   // 4 / 5: A/B switches
-    const long long nblk = (p.xcd_slices ? ((zs + 7) / 8) * 8 : zs) * p.o_tiles * p.i_tiles * kh * kw;
-    if (zs > (1 << 24) || nblk >= (1ll << 31) || chunks_per_out > (1 << 24)) return MSG_EUNSUPPORTED;
-    *need = p.split ? zs * p.slab : 0;
-    if (plan_only) return MSG_OK;
-    if (p.split && (!ws || ws_floats < *need)) return MSG_EINVAL;
-    dim3 grid((unsigned)nblk);
-    hipStream_t s = (hipStream_t)stream;
+    const long long chunks_per_out = q.per_sample ? q.k_chunks : zs;
+    *plan = WgradPlan{};
     // Register staging keeps two K-steps of loads in flight; measured faster here than LDS-DMA with one step in
     // flight (685 vs 608 TFLOP/s at 3x3 512->512 @256^2): both operands of this kernel stream from beyond L2.
-    const bool dma = variant == 1;                   // MSG_CONV_VARIANT=1 forces LDS-DMA staging, 2 the generic addressing (A/B)
-    if (dtype == MSG_BF16) {
+    plan->kernel = variant == 1 && !q.split ? WGRAD_DMA : uni ? WGRAD_UNI : WGRAD_GENERIC;
+    plan->nz = (int)zs; plan->chunks_per_out = (int)chunks_per_out; plan->n_out = q.per_sample ? B : 1;
+    plan->slice_pixels = slice_pixels; plan->OWv = owv; plan->OHv = ohv; plan->fold = fold;
+    plan->xcd_slices = (tiles <= slice_tiles && variant != 4 && (slice_tiles == 1 || zs % 8 == 0 || zs >= 64)) ||
+                       (variant == 5 && zs % 8 == 0);
+    plan->blocks = (plan->xcd_slices ? ((zs + 7) / 8) * 8 : zs) * tiles * taps;
+    plan->need = chunks_per_out > 1 ? zs * q.slab() : 0;
+    plan->supported = !(zs > (1 << 24) || plan->blocks >= (1ll << 31) || chunks_per_out > (1 << 24));
+    return true;
+}
+
+static void conv_wgrad_generic_launch(const WgradProblem& q, const WgradPlan& plan, const void* gy, const void* x, float* gw,
+                                      float* ws, void* stream) {
+    WgradParams p{};
+    p.B = q.B; p.IH = q.IH; p.IW = q.IW; p.Cx = q.Cx; p.I = q.I; p.OH = q.OH; p.OW = q.OW; p.ldgy = q.ldgy; p.O = q.O;
+    p.kh = q.kh; p.kw = q.kw; p.stride = q.stride; p.pad = q.pad; p.pixel_shuffle = q.pixel_shuffle;
+    p.per_sample = q.per_sample; p.ldgw = q.ldgw; p.oi_major = q.oi_major; p.gain = q.gain;
+    p.o_tiles = (q.O + WT - 1) / WT; p.i_tiles = (q.I + WT - 1) / WT; p.gw_zstride = q.gw_zstride(); p.slab = q.slab();
+    p.OWv = plan.OWv; p.OHv = plan.OHv; p.pix_per_chunk = plan.slice_pixels; p.nz = plan.nz; p.fold = plan.fold;
+    p.chunks_per_sample = plan.fold ? plan.nz : q.k_chunks; p.split = plan.chunks_per_out > 1; p.xcd_slices = plan.xcd_slices;
+    const dim3 grid((unsigned)plan.blocks);
+    hipStream_t s = (hipStream_t)stream;
+    const bool dma = plan.kernel == WGRAD_DMA, uni = plan.kernel == WGRAD_UNI;
+    if (q.dtype == MSG_BF16) {
         if (dma) hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, true, false>), grid, dim3(256), 0, s, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
         else if (uni) hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, false, true>), grid, dim3(256), 0, s, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
         else hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, false, false>), grid, dim3(256), 0, s, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
-    } else if (split == 3) {
+    } else if (q.split == 3) {
         if (uni) hipLaunchKernelGGL((conv_wgrad_kernel<float, false, true, 3>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
         else hipLaunchKernelGGL((conv_wgrad_kernel<float, false, false, 3>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
     } else {
@@ -654,9 +618,15 @@ static int wgrad_impl(const WgradProblem& q, const void* gy, const void* x, floa
         else if (uni) hipLaunchKernelGGL((conv_wgrad_kernel<float, false, true>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
         else hipLaunchKernelGGL((conv_wgrad_kernel<float, false, false>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
     }
-    const int rc = MSG_CHECK_LAUNCH();
-    if (rc != MSG_OK || !p.split) return rc;
-    return msg_wgrad_reduce_launch(ws, gw, p.slab, n_out, (int)chunks_per_out, O, kh * kw, I, ldgw, oi_major, stream);
+}
+
+// The only place that knows the order of the weight-gradient kernels.
+WgradPlan conv_wgrad_select(const WgradProblem& q) {
+    WgradPlan plan{};                                               // (an empty batch: nothing to launch)
+    plan.supported = true;
+    if (q.B == 0 || conv_wgrad_row3_eligible(q, &plan)) return plan;   // kh x 3 'same' convs on wide maps: three taps per workgroup
+    conv_wgrad_generic_eligible(q, &plan);                             // everything else: 128 x 128 tile of one tap
+    return plan;
 }
 
 static WgradProblem wgrad_problem(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy, int O, int ldgw,
@@ -667,13 +637,50 @@ static WgradProblem wgrad_problem(int dtype, int B, int IH, int IW, int Cx, int 
                         per_sample, k_chunks, oi_major, gain};
 }
 
+// The argument checks of the three entries, in the order their codes are promised: MSG_EINVAL before MSG_EUNSUPPORTED; the
+// pointers of a launch (`io`: gy, x, gw, ws; NULL for the queries) between the two.  An empty batch is MSG_OK whatever the rest.
+static int wgrad_check(const WgradProblem& q, const void* const* io) {
+    if (q.B == 0) return MSG_OK;
+    if (q.B < 0 || q.IH <= 0 || q.IW <= 0 || q.OH <= 0 || q.OW <= 0 || q.O <= 0 || q.I <= 0 || q.kh <= 0 || q.kw <= 0 ||
+        q.stride <= 0 || q.Cx <= 0 || q.ldgy <= 0 || q.ldgw < q.I || q.ldgw % 4 || q.k_chunks <= 0)
+        return MSG_EINVAL;
+    if (io && (!io[0] || !io[1] || !io[2])) return MSG_EINVAL;
+    if (q.dtype != MSG_F32 && q.dtype != MSG_BF16) return MSG_EUNSUPPORTED;
+    const int vec = 16 / q.esz();
+    if (q.Cx % vec || q.ldgy % vec) return MSG_EUNSUPPORTED;
+    if (io && (((uintptr_t)io[0] | (uintptr_t)io[1] | (uintptr_t)io[2] | (uintptr_t)io[3]) & 15u)) return MSG_EUNSUPPORTED;
+    return MSG_OK;
+}
+
+// checks + selection: MSG_OK and the plan, or the code of a call that stops before the plan is used
+static int wgrad_plan_for(const WgradProblem& q, const void* const* io, WgradPlan* plan) {
+    const int rc = wgrad_check(q, io);
+    if (rc != MSG_OK) return rc;
+    *plan = conv_wgrad_select(q);
+    return plan->supported ? MSG_OK : MSG_EUNSUPPORTED;
+}
+
 extern "C" long long msg_conv2d_wgrad_workspace(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy,
                                                 int O, int ldgw, int kh, int kw, int stride, int pad, int pixel_shuffle,
                                                 int per_sample, int k_chunks) {
-    long long need = 0;
-    const int rc = wgrad_impl(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
-                                            per_sample, k_chunks, 0, 1.f), nullptr, nullptr, nullptr, nullptr, 0, 1, &need, nullptr);
-    return rc == MSG_OK ? need : (long long)rc;
+    WgradPlan plan;
+    const int rc = wgrad_plan_for(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
+                                                per_sample, k_chunks, 0, 1.f), nullptr, &plan);
+    return rc == MSG_OK ? plan.need : (long long)rc;
+}
+
+// The plan msg_conv2d_wgrad would launch (no launch), in the order of MSG_WPLAN_FIELDS of msg_hip.h.
+extern "C" int msg_conv2d_wgrad_plan(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy,
+                                     int O, int ldgw, int kh, int kw, int stride, int pad, int pixel_shuffle,
+                                     int per_sample, int k_chunks, long long* out, int n_out_fields) {
+    WgradPlan plan;
+    const int rc = wgrad_plan_for(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
+                                                per_sample, k_chunks, 0, 1.f), nullptr, &plan);
+    if (rc != MSG_OK) return rc;
+    const long long fields[MSG_WPLAN_FIELDS] = {plan.kernel, plan.nz, plan.chunks_per_out, plan.n_out, plan.slice_pixels, plan.OWv,
+                                                plan.OHv, plan.fold, plan.xcd_slices, plan.blocks, plan.need};
+    for (int k = 0; k < MSG_WPLAN_FIELDS && k < n_out_fields; ++k) out[k] = fields[k];
+    return MSG_OK;
 }
 
 extern "C" int msg_conv2d_wgrad(const void* gy, const void* x, float* gw, int dtype,
@@ -681,7 +688,16 @@ extern "C" int msg_conv2d_wgrad(const void* gy, const void* x, float* gw, int dt
                                 int kh, int kw, int stride, int pad, int pixel_shuffle,
                                 int per_sample, int k_chunks, int oi_major, float gain,
                                 float* ws, long long ws_floats, void* stream) {
-    long long need = 0;
-    return wgrad_impl(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle, per_sample,
-                                    k_chunks, oi_major, gain), gy, x, gw, ws, ws_floats, 0, &need, stream);
+    const WgradProblem q = wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle, per_sample,
+                                         k_chunks, oi_major, gain);
+    const void* const io[4] = {gy, x, gw, ws};
+    WgradPlan plan;
+    int rc = wgrad_plan_for(q, io, &plan);
+    if (rc != MSG_OK || !plan.blocks) return rc;                    // (no blocks: an empty batch)
+    if (plan.need && (!ws || ws_floats < plan.need)) return MSG_EINVAL;
+    if (plan.kernel == WGRAD_ROW3 || plan.kernel == WGRAD_ROW3_W32) conv_wgrad_row3_launch(q, plan, gy, x, gw, ws, stream);
+    else conv_wgrad_generic_launch(q, plan, gy, x, gw, ws, stream);
+    rc = MSG_CHECK_LAUNCH();
+    if (rc != MSG_OK || !plan.need) return rc;
+    return wgrad_reduce_launch(q, plan, ws, gw, stream);
 }

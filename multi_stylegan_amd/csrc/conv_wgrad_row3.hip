@@ -16,6 +16,7 @@
 // same buffer-load addressing (per-thread constant offset + wave-uniform SGPR cursor, out-of-range rows read zeros),
 // same fp32 epilogue (plain stores into GW[o][tap][i], or into the K-slice's slab when the sum is split: conv_wgrad.hip).
 #include "conv_dispatch.h"
+#include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -336,95 +337,60 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
     }
 }
 
-// Called by msg_conv2d_wgrad (conv_wgrad.hip) after its argument checks; returns 1 if the geometry is this file's (planned,
-// and launched unless plan_only), 0 if not, a negative MSG_E* code on error.  *need = workspace floats (0: no split).
-int conv_wgrad_row3_try(const WgradProblem& q, const void* gy, const void* x, float* gw, float* ws, long long ws_floats,
-                        int plan_only, long long* need, void* stream) {
-    const int dtype = q.dtype, B = q.B, IH = q.IH, IW = q.IW, Cx = q.Cx, I = q.I, OH = q.OH, OW = q.OW, ldgy = q.ldgy, O = q.O,
-              ldgw = q.ldgw, kh = q.kh, kw = q.kw, stride = q.stride, pad = q.pad, pixel_shuffle = q.pixel_shuffle,
-              per_sample = q.per_sample, oi_major = q.oi_major;
-    int k_chunks = q.k_chunks;
+// All of this kernel's conditions; on yes the plan is filled.  It declines -- the generic kernel takes over, no error -- for
+// geometries that are not its own, for tensors that reach 2^31 - 16 bytes behind one descriptor, and for a K split (chosen
+// first) that exceeds its grid limits.
+bool conv_wgrad_row3_eligible(const WgradProblem& q, WgradPlan* plan) {
     static const int enabled = msg_tunable("MSG_WGRAD_ROW3", 1);
     static const int w32_on = msg_tunable("MSG_WGRAD_ROW3_W32", 1);                         // MSG_WGRAD_ROW3_W32=0: 32-wide maps stay on conv_wgrad_kernel (A/B)
-    const bool w32 = w32_on && OW == 32 && OH % 2 == 0;
-    if (!enabled || dtype != MSG_BF16 || kw != 3 || stride != 1 || pixel_shuffle || (OW % R3_KP && !w32) || IH != OH ||
-        IW != OW || pad != 1 || kh > 3)
-        return 0;
+    const bool w32 = w32_on && q.OW == 32 && q.OH % 2 == 0;
+    if (!enabled || q.dtype != MSG_BF16 || q.kw != 3 || q.stride != 1 || q.pixel_shuffle || (q.OW % R3_KP && !w32) || q.IH != q.OH ||
+        q.IW != q.OW || q.pad != 1 || q.kh > 3)
+        return false;
     // (the 'same' geometry: horizontal padding 1 is what the shifted-row trick assumes; vertical padding is free)
-    const long long gy_bytes = (long long)OH * OW * ldgy * 2, x_bytes = (long long)IH * IW * Cx * 2;
-    const long long nb = per_sample ? 1 : B;
     // (31-bit offsets over everything one descriptor spans -- a sample, or the whole batch when it is folded into K: the SGPR
     //  cursor counts against the descriptor's range like the per-lane offset)
-    if (nb * gy_bytes >= 0x7ffffff0ll || nb * x_bytes >= 0x7ffffff0ll) return 0;
-    Row3Params p{};
-    p.B = B; p.H = OH; p.W = OW; p.Cx = Cx; p.I = I; p.ldgy = ldgy; p.O = O; p.ldgw = ldgw;
-    p.kh = kh; p.pad = pad;
-    p.per_sample = per_sample;
-    p.o_tiles = (O + 127) / 128;
-    p.i_tiles = (I + 127) / 128;
-    p.oi_major = oi_major;
-    p.gain = q.gain;
-    p.gw_zstride = oi_major ? (long long)O * I * kh * 3 : (long long)O * kh * 3 * ldgw;
-    p.slab = (long long)O * kh * 3 * ldgw;
-    const long long steps_per_sample = w32 ? OH / 2 : (long long)OH * (OW / R3_KP);
-    const long long tiles = (long long)p.o_tiles * p.i_tiles * kh;
-    long long zs, chunks_per_out;
-    if (per_sample) {
-        // the caller's k_chunks, or -- when it has no opinion (1) -- the same wave-quantisation model as below over this
+    const long long nb = q.per_sample ? 1 : q.B;
+    if (nb * q.gy_bytes() >= 0x7ffffff0ll || nb * q.x_bytes() >= 0x7ffffff0ll) return false;
+    const long long steps_per_sample = w32 ? q.OH / 2 : (long long)q.OH * (q.OW / R3_KP);
+    const long long tiles = (long long)((q.O + 127) / 128) * ((q.I + 127) / 128) * q.kh;
+    long long steps_per_chunk, chunks;
+    if (q.per_sample) {
+        // the caller's k_chunks, or -- when it has no opinion (1) -- the wave-quantisation model of conv_wgrad_ksplit over this
         // kernel's ONE workgroup per CU: B * tiles workgroups in rounds of 256.  Batch 16 x 512 -> 512 is 768 workgroups = three
         // full rounds; batch 8 (the path-length pass works on half a batch) is 384 = one and a half, i.e. a quarter of the
         // launch on half-empty hardware (round 5: 1 101 TFLOP/s against 1 352 at batch 16); two K-slices per sample make it
         // three full rounds again, for one extra pass over the 9.4-MB slabs (priced at 12 K-steps: with 6 the 64-step sweeps of the 64^2 maps were split too and lost 17 %).
-        if (k_chunks <= 1) {
-            static const int slab_cost_ps = msg_tunable("MSG_WGRAD3_SLAB_COST_PS", 12);
-            long long best = -1;
-            for (long long c = 1; c <= 4 && c * 8 <= steps_per_sample; ++c) {
-                const long long rounds = ((long long)B * tiles * c + 255) / 256;
-                const long long cost = rounds * ((steps_per_sample + c - 1) / c + 3 + (c > 1 ? slab_cost_ps : 0));
-                if (best < 0 || cost < best) { best = cost; k_chunks = (int)c; }
-            }
-        }
-        p.chunks_per_sample = k_chunks;
-        p.steps_per_chunk = (int)((steps_per_sample + k_chunks - 1) / k_chunks);
-        zs = (long long)B * k_chunks;
-        chunks_per_out = k_chunks;
+        static const int slab_cost_ps = msg_tunable("MSG_WGRAD3_SLAB_COST_PS", 12);
+        const long long most = steps_per_sample / 8 < 4 ? steps_per_sample / 8 : 4;
+        chunks = q.k_chunks > 1 ? q.k_chunks : conv_wgrad_ksplit(steps_per_sample, q.B * tiles, {256, 3, slab_cost_ps, most, LLONG_MAX, false});
+        steps_per_chunk = (steps_per_sample + chunks - 1) / chunks;
     } else {
-        // shared weights: the batch is folded into K; K split by the wave-quantisation cost model of conv_wgrad.hip
-        // with ONE workgroup per CU (rounds of 256), ~3 steps of fixed cost per workgroup and, when the sum is split, the
-        // write + read of a workgroup's three 64-KiB slab tiles (~MSG_WGRAD3_SLAB_COST steps)
+        // shared weights: the batch is folded into K; the same model with ~3 steps of fixed cost per workgroup and, when the sum
+        // is split, the write + read of a workgroup's three 64-KiB slab tiles (~MSG_WGRAD3_SLAB_COST steps)
         static const int slab_cost = msg_tunable("MSG_WGRAD3_SLAB_COST", 4);
-        const long long steps = (long long)B * steps_per_sample;
-        long long chunks = 1, best = -1;
-        const long long cmax = steps / 4 < 4096 ? steps / 4 : 4096;
-        for (long long c = 1; c <= cmax; ++c) {
-            const long long rounds = (tiles * c + 255) / 256;
-            const long long cost = rounds * ((steps + c - 1) / c + 3 + (c > 1 ? slab_cost : 0));
-            if (best < 0 || cost < best) { best = cost; chunks = c; }
-            if (tiles * c > 4096) break;
-        }
-        p.steps_per_chunk = (int)((steps + chunks - 1) / chunks);
-        zs = (steps + p.steps_per_chunk - 1) / p.steps_per_chunk;
-        p.chunks_per_sample = (int)zs;
-        chunks_per_out = zs;
+        const long long steps = (long long)q.B * steps_per_sample;
+        const long long want = conv_wgrad_ksplit(steps, tiles, {256, 3, slab_cost, steps / 4 < 4096 ? steps / 4 : 4096, 4096, false});
+        steps_per_chunk = (steps + want - 1) / want;
+        chunks = (steps + steps_per_chunk - 1) / steps_per_chunk;
     }
-    p.split = chunks_per_out > 1;
-    p.nz = (int)zs;
-    const long long nblk = zs * tiles;
-    if (zs > (1 << 24) || nblk >= (1ll << 31)) return 0;
-    *need = p.split ? zs * p.slab : 0;
-    if (plan_only) return 1;
-    if (p.split && (!ws || ws_floats < *need)) return MSG_EINVAL;
-    if (w32)
-        hipLaunchKernelGGL(conv_wgrad_row3s_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
-    else
-        hipLaunchKernelGGL(conv_wgrad_row3s_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
-    if (MSG_CHECK_LAUNCH() != MSG_OK) return MSG_ELAUNCH;
-    if (p.split) {
-        const int rc = msg_wgrad_reduce_launch(ws, gw, p.slab, per_sample ? B : 1, (int)chunks_per_out, O, kh * 3, I, ldgw,
-                                               oi_major, stream);
-        if (rc != MSG_OK) return rc;
-    }
-    return 1;
+    const long long zs = q.per_sample ? q.B * chunks : chunks;
+    if (zs > (1 << 24) || zs * tiles >= (1ll << 31)) return false;
+    *plan = WgradPlan{};
+    plan->kernel = w32 ? WGRAD_ROW3_W32 : WGRAD_ROW3;
+    plan->nz = (int)zs; plan->chunks_per_out = (int)chunks; plan->n_out = q.per_sample ? q.B : 1;
+    plan->slice_pixels = (int)steps_per_chunk * R3_KP; plan->OWv = q.OW; plan->OHv = q.OH; plan->fold = !q.per_sample;
+    plan->blocks = zs * tiles; plan->need = chunks > 1 ? zs * q.slab() : 0; plan->supported = true;
+    return true;
+}
+
+void conv_wgrad_row3_launch(const WgradProblem& q, const WgradPlan& plan, const void* gy, const void* x, float* gw, float* ws,
+                            void* stream) {
+    Row3Params p{};
+    p.B = q.B; p.H = q.OH; p.W = q.OW; p.Cx = q.Cx; p.I = q.I; p.ldgy = q.ldgy; p.O = q.O; p.ldgw = q.ldgw;
+    p.kh = q.kh; p.pad = q.pad; p.per_sample = q.per_sample; p.oi_major = q.oi_major; p.gain = q.gain;
+    p.o_tiles = (q.O + 127) / 128; p.i_tiles = (q.I + 127) / 128; p.gw_zstride = q.gw_zstride(); p.slab = q.slab();
+    p.steps_per_chunk = plan.slice_pixels / R3_KP; p.chunks_per_sample = plan.chunks_per_out; p.nz = plan.nz; p.split = plan.chunks_per_out > 1;
+    auto* kernel = plan.kernel == WGRAD_ROW3_W32 ? conv_wgrad_row3s_kernel<true> : conv_wgrad_row3s_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan.blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
 }

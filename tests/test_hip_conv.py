@@ -157,6 +157,61 @@ def test_conv_primitives_split_bf16_products(case, per_sample, mode="split_bf16x
     assert any(not torch.equal(a, e) for a, e in zip(split, exact)), "the split products did not run"
 
 
+PLAN_BRANCHES = [  # name, storage, contraction mode, per-sample, H, W, k, pixel shuffle, gain, what the plan must say
+    ("row3_shared", torch.bfloat16, None, False, 8, 64, 3, False, 0.5, dict(kernel="ROW3", fold=1, split=True)),
+    ("row3_per_sample", torch.bfloat16, None, True, 8, 64, 3, False, 1.0, dict(kernel="ROW3", fold=0, n_out=2)),
+    ("row3_w32", torch.bfloat16, None, False, 8, 32, 3, False, 1.0, dict(kernel="ROW3_W32", fold=1)),
+    ("uniform_rows", torch.bfloat16, None, False, 16, 16, 3, False, 1.0, dict(kernel="UNI", OWv=16, OHv=16)),
+    ("padded_rows", torch.bfloat16, None, False, 15, 15, 3, False, 1.0, dict(kernel="UNI", OWv=16, OHv=16)),
+    ("generic_folded", torch.bfloat16, None, False, 12, 24, 3, False, 1.0, dict(kernel="GENERIC", fold=1)),
+    ("pixel_shuffle", torch.bfloat16, None, False, 8, 8, 2, True, 1.0, dict(kernel="UNI", blocks=4)),
+    ("fp32_exact", torch.float32, "exact", False, 16, 16, 3, False, 1.0, dict(kernel="UNI")),
+    ("split_bf16x3", torch.float32, "split_bf16x3", False, 16, 16, 3, False, 1.0, dict(kernel="UNI")),
+    ("per_sample_two_chunks", torch.bfloat16, None, True, 32, 64, 1, False, 1.0, dict(kernel="UNI", fold=0, chunks_per_out=2, split=True)),
+    ("oi_major_gain_split", torch.bfloat16, None, False, 32, 32, 1, False, 0.5, dict(kernel="UNI", fold=1, xcd_slices=1, split=True)),
+]
+
+
+@pytest.mark.parametrize("case", PLAN_BRANCHES, ids=[c[0] for c in PLAN_BRANCHES])
+def test_weight_gradient_plan_branches(case):
+    """One weight gradient per branch of the plan (conv_wgrad_select), B = 2, 64 -> 64 channels: msg_conv2d_wgrad_plan says the
+    case lands in the branch it is meant for, and conv_ops._launch_wgrad -- the plan's fields copied into the kernel's parameter
+    struct: slab, strides, gain, tiles, which the query cannot see -- gives the float64 torch.nn.grad.conv2d_weight of the same
+    operands, at the weight-gradient tolerance of test_conv_primitives for the storage type."""
+    import ctypes
+    from multi_stylegan_amd import _lib, conv_ops
+    name, dtype, mode, per_sample, h, w_, k, shuffle, gain, expect = case
+    b, i, o = 2, 64, 64
+    pad = 0 if shuffle else k // 2
+    g = torch.Generator().manual_seed(len(name) * 13)
+    x = torch.randn(b, i, h, w_, generator=g).to(dtype)
+    gy = torch.randn(b, o, *((2 * h, 2 * w_) if shuffle else (h, w_)), generator=g).to(dtype)
+    # the geometry _launch_wgrad passes, asked of the plan query first
+    kp = 64 if dtype == torch.bfloat16 else 32
+    code = {None: _lib.MSG_BF16, "exact": _lib.MSG_F32, "split_bf16x3": _lib.MSG_F32_SPLIT}[mode]
+    geom = (code, b, h, w_, i, i, h, w_, o, o, i, k, k, 1, pad, int(shuffle), int(per_sample),
+            conv_ops.wgrad_k_chunks(b, o, i, k * k, h, w_, per_sample, kp))
+    out = (ctypes.c_longlong * _lib.MSG_WPLAN_FIELDS)()
+    assert _lib.lib().msg_conv2d_wgrad_plan(*geom, ctypes.addressof(out), len(out)) == _lib.MSG_OK
+    plan = dict(zip(("kernel", "nz", "chunks_per_out", "n_out", "slice_pixels", "OWv", "OHv", "fold", "xcd_slices", "blocks", "need"), out))
+    plan["split"] = plan["need"] > 0
+    want = dict(expect, kernel=getattr(_lib, "MSG_WPLAN_" + expect["kernel"]))
+    assert {key: plan[key] for key in want} == want, plan
+    assert plan["need"] == _lib.lib().msg_conv2d_wgrad_workspace(*geom)
+
+    def ref(xb, gb):                                                    # float64, one weight set
+        if shuffle:      # tap (dy, dx) pairs x[h, w] with gy[2h + dy, 2w + dx]: the weight gradient of a stride-2 conv FROM gy TO x
+            return torch.nn.grad.conv2d_weight(gb, (i, o, 2, 2), xb, stride=2).transpose(0, 1)
+        return torch.nn.grad.conv2d_weight(xb, (o, i, k, k), gb, padding=pad)
+    xr, gr = x.double(), gy.double()
+    gw_r = gain * (torch.stack([ref(xr[n:n + 1], gr[n:n + 1]) for n in range(b)]) if per_sample else ref(xr, gr))
+    cl = lambda t: t.to(DEV).contiguous(memory_format=torch.channels_last)
+    gw = conv_ops._launch_wgrad(cl(gy), cl(x), o, i, k, k, 1, pad, shuffle, per_sample, (h, w_) if shuffle else None, gain=gain,
+                                mode=mode)
+    assert gw.shape == gw_r.shape
+    assert rel_err(gw, gw_r) < TOLS[dtype], (name, rel_err(gw, gw_r))
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_conv2d_bias_and_linear(dtype):
     from multi_stylegan_amd import conv_ops

@@ -51,6 +51,7 @@ def test_binding_types_are_the_headers():
     assert res is I and len(args) == 22 and args[:5] == [P, P, P, P, I] and args[5:20] == [I] * 15
     assert args[20] is L and args[21] is P                                   # w_batch_stride, stream
     assert sig["msg_conv2d_fprop_plan"] == (I, [I] * 11 + [L])
+    assert sig["msg_conv2d_wgrad_plan"] == (I, [I] * 18 + [P, I]) and sig["msg_conv2d_wgrad_workspace"] == (L, [I] * 18)
     assert sig["msg_flat_adam"] == (I, [P, P, P, P, P, L, P, F, F, F, F, I, F, P])
     assert sig["msg_flat_ema"] == (I, [P, P, L, F, P])
     assert sig["msg_bias_act_backward_workspace"] == (L, [L, I, I, I])
@@ -416,7 +417,7 @@ def test_kernel_plans_respect_the_31_bit_offset_limits():
 
 def test_dispatch_answers_match_the_recorded_table():
     """The host-side answers of the convolution family -- msg_conv2d_fprop_plan, msg_conv2d_fprop_act_backward_workspace,
-    msg_conv2d_fprop_upconv_eligible, msg_conv2d_fprop_thin_eligible, msg_conv2d_wgrad_workspace -- over the grid of
+    msg_conv2d_fprop_upconv_eligible, msg_conv2d_fprop_thin_eligible, msg_conv2d_wgrad_workspace, msg_conv2d_wgrad_plan -- over the grid of
     tools/gen_dispatch_table.py (the models' geometries at 256^2 and 512^2, shared and per-sample weights, batch 1 .. 33, and both
     sides of every eligibility threshold), against tests/golden/dispatch_table.json: the answers recorded BEFORE the forward dispatch
     became one selection function.  Equality on every row, except four classes where the recorded answer named a kernel the
@@ -435,11 +436,12 @@ def test_dispatch_answers_match_the_recorded_table():
     lib = _lib.lib()
     with open(os.path.join(GOLDEN, "dispatch_table.json")) as f:
         table = json.load(f)
-    rows = {name: fn() for name, fn in grid.ROWS.items()}
+    rows = {name: fn() for name, fn in grid.ALL_ROWS.items()}
     for name, r in rows.items():                       # the recorded answers belong to exactly these rows
         assert grid.digest(r) == table["digest"][name] and len(r) == len(table[name]), name
     assert not grid.missing_profile_geometries([os.path.join(ROOT, "profiles", "r05_shape_table.txt"),
                                                 os.path.join(ROOT, "profiles", "r05_shape_table_regularised.txt")])
+    bf16 = _lib.MSG_BF16
     thin_kc = (2, 4, 6, 8, 12, 16)
     model_channels = (8, 64, 128, 256, 384, 512, 768, 1024)
     truthful = {"plan": 0, "thin_eligible": 0, "upconv_eligible": 0}
@@ -472,10 +474,72 @@ def test_dispatch_answers_match_the_recorded_table():
     for args, need in zip(rows["wgrad_workspace"], table["wgrad_workspace"]):
         if lib.msg_conv2d_wgrad_workspace(*args) != need:
             bad.append(("wgrad_workspace", args, need, lib.msg_conv2d_wgrad_workspace(*args)))
+    # weight-gradient plans, recorded from the commit before msg_conv2d_wgrad planned through conv_wgrad_select (its wgrad_impl /
+    # conv_wgrad_row3_try, with a query that reported their locals): every field of every row, no exceptions
+    for args, ans in zip(rows["wgrad_plan"], table["wgrad_plan"]):
+        if grid.wgrad_plan(lib, args) != ans:
+            bad.append(("wgrad_plan", args, ans, grid.wgrad_plan(lib, args)))
     assert not bad, (len(bad), bad[:10])
     assert len(rows["plan"]) > 2500 and len(rows["wgrad_workspace"]) > 1400
+    assert rows["wgrad_plan"][:len(rows["wgrad_workspace"])] == rows["wgrad_workspace"]
+    # ... and the grid reaches every branch of the plan (MSG_WPLAN_DMA needs a tuning build's MSG_CONV_VARIANT=1: not covered)
+    plans = [(a, p) for a, p in zip(rows["wgrad_plan"], table["wgrad_plan"]) if isinstance(p, list) and a[1] > 0]
+    kernel, nz, chunks_per_out, n_out, slice_pixels, owv, ohv, fold, xcd_slices, blocks, need = range(_lib.MSG_WPLAN_FIELDS)
+    assert {p[kernel] for _a, p in plans} == {_lib.MSG_WPLAN_GENERIC, _lib.MSG_WPLAN_UNI, _lib.MSG_WPLAN_ROW3, _lib.MSG_WPLAN_ROW3_W32}
+    assert {p[fold] for _a, p in plans} == {0, 1} and {p[xcd_slices] for _a, p in plans} == {0, 1}
+    assert any(p[owv] != a[7] for a, p in plans) and any(p[ohv] != a[6] for a, p in plans)      # padded rows (15 wide gives both)
+    row3 = (_lib.MSG_WPLAN_ROW3, _lib.MSG_WPLAN_ROW3_W32)
+    # per-sample weights, k_chunks 1: the row-sharing kernel chose the split (batch 8, 512 -> 512 @128^2: two K-slices per sample)
+    own = {tuple(a): p for a, p in plans if p[kernel] in row3 and a[16] and a[17] == 1 and p[chunks_per_out] > 1}
+    assert own[(bf16, 8, 128, 128, 512, 512, 128, 128, 512, 512, 512, 3, 3, 1, 1, 0, 1, 1)][chunks_per_out] == 2
+    # the row-sharing kernel's geometry handed to the 128 x 128 kernel: 2 GiB behind one descriptor (shared weights: the batch)
+    handed = [a for a, p in plans if p[kernel] not in row3 and a[0] == bf16 and a[11:16] == [3, 3, 1, 1, 0] and a[7] % 64 == 0 and
+              a[2:4] == a[6:8] and not a[16] and a[1] * a[6] * a[7] * max(a[4], a[8]) * 2 >= 0x7ffffff0]
+    assert handed and len(handed) == sum(1 for a, p in plans if a[0] == bf16 and a[11:16] == [3, 3, 1, 1, 0] and a[7] % 64 == 0 and
+                                         a[2:4] == a[6:8] and not a[16] and p[kernel] not in row3)
+    refused = [p for p in table["wgrad_plan"] if not isinstance(p, list)]
+    assert _lib.MSG_EINVAL in refused and _lib.MSG_EUNSUPPORTED in refused
     # the exceptions are exactly the rows the four classes describe (thin-N + split + 65536-sample plans; thin queries; up-conv queries)
     assert truthful == {"plan": 60 + 51 + 2, "thin_eligible": 20, "upconv_eligible": 2}, truthful
+
+
+def test_weight_gradient_codes_before_any_launch():
+    """What msg_conv2d_wgrad answers without reaching a launch, on a geometry of the row-sharing kernel and one of the 128 x 128
+    kernel whose sums are split: the codes the commit before conv_wgrad_select returned for the same calls (MSG_EINVAL argument
+    checks before MSG_EUNSUPPORTED; alignment only with pointers; the workspace after the plan).  The pointers are fake, 16-byte
+    aligned integers: every case returns before one is used."""
+    from multi_stylegan_amd import _lib
+    from multi_stylegan_amd.build import build
+    from tools.gen_dispatch_table import wgrad_plan
+    build(verbose=False)
+    lib = _lib.lib()
+    OK, EINVAL, EUNSUPPORTED = _lib.MSG_OK, _lib.MSG_EINVAL, _lib.MSG_EUNSUPPORTED
+    gy, x, gw, ws = 0x10000, 0x20000, 0x30000, 0x40000
+    #        dtype          B  IH  IW  Cx  I   OH  OW ldgy  O ldgw kh kw s  p ps per-sample k_chunks
+    geoms = {_lib.MSG_WPLAN_ROW3: [_lib.MSG_BF16, 2, 8, 64, 64, 64, 8, 64, 64, 64, 64, 3, 3, 1, 1, 0, 0, 2],
+             _lib.MSG_WPLAN_UNI: [_lib.MSG_BF16, 2, 32, 32, 64, 64, 32, 32, 64, 64, 64, 1, 1, 1, 0, 0, 0, 4]}
+    for kernel, geom in geoms.items():
+        plan = wgrad_plan(lib, geom)
+        need = plan[10]
+        assert plan[0] == kernel and plan[2] > 1 and need > 0 and need == lib.msg_conv2d_wgrad_workspace(*geom)
+
+        def call(geom=geom, gy=gy, gw=gw, ws=ws, ws_floats=need):
+            return lib.msg_conv2d_wgrad(gy, x, gw, *geom, 1, 0.5, ws, ws_floats, None)
+
+        def changed(index, value):
+            return geom[:index] + [value] + geom[index + 1:]
+        assert call(gy=None) == EINVAL
+        assert call(geom=changed(10, 60)) == EINVAL                     # ldgw < I
+        assert call(geom=changed(10, 66)) == EINVAL                     # ldgw % 4
+        assert call(gw=gw + 4) == EUNSUPPORTED                          # a misaligned gradient
+        assert call(ws=None) == EINVAL
+        assert call(ws_floats=need - 1) == EINVAL
+        assert call(geom=changed(1, 0)) == OK                           # an empty batch
+        assert call(geom=changed(1, 0), gy=None, ws=None, ws_floats=0) == OK
+        assert call(geom=changed(17, 0)) == EINVAL                      # k_chunks
+        # the queries answer the same codes for what they can see
+        assert lib.msg_conv2d_wgrad_workspace(*changed(10, 60)) == EINVAL and wgrad_plan(lib, changed(17, 0)) == EINVAL
+        assert lib.msg_conv2d_wgrad_workspace(*changed(1, 0)) == 0 and wgrad_plan(lib, changed(1, 0)) == [0] * _lib.MSG_WPLAN_FIELDS
 
 
 def test_non_square_conv_geometry_is_refused():

@@ -1,9 +1,9 @@
 """Record what the host-side dispatch of the convolution family answers, over a grid of problems, into
 tests/golden/dispatch_table.json (replayed by tests/test_host.py::test_dispatch_answers_match_the_recorded_table).
 
-    python -m tools.gen_dispatch_table [--out tests/golden/dispatch_table.json]
+    python -m tools.gen_dispatch_table [--out tests/golden/dispatch_table.json] [--only TABLE]
 
-Host-only: the five queried entries launch nothing, so no GPU is needed.  The grid (the *_rows functions below; a few thousand
+Host-only: the six queried entries launch nothing, so no GPU is needed.  The grid (the *_rows functions below; a few thousand
 rows): every convolution geometry the two networks issue at 256^2 / batch 16 (+ the discriminator's doubled batch) and 512^2 /
 batch 8 -- forward, data gradient, stride-2 data gradient, sub-pixel up-convolution, the thin RGB / head layers -- with shared and
 per-sample weights at batch 1, 4, 8, 16, 32, 33, and one value on each side of every threshold of the eligibility functions.
@@ -167,13 +167,8 @@ def thin_rows():
 
 def model_k_chunks(b, o, i, taps, oh, ow, per_sample, kp=64):
     """The K split conv_ops._launch_wgrad asks for (bf16: 64 pixels per K-step)."""
-    tiles = ((o + 127) // 128) * ((i + 127) // 128) * taps * b
-    if per_sample:
-        return max(1, min((oh * ow) // (16 * kp), 1024 // tiles)) if tiles < 256 else 1
-    k = max(1, min((oh * ow + 4 * kp - 1) // (4 * kp), (1024 + tiles - 1) // tiles))
-    while b * k > 65535:
-        k -= 1
-    return k
+    from multi_stylegan_amd.conv_ops import wgrad_k_chunks
+    return wgrad_k_chunks(b, o, i, taps, oh, ow, per_sample, kp)
 
 
 def missing_profile_geometries(paths):
@@ -251,7 +246,56 @@ def wgrad_rows():
     return rows
 
 
+def wgrad_plan_extra_rows():
+    """Arguments of msg_conv2d_wgrad_plan beyond wgrad_rows(): the branches of the plan that the workspace size cannot tell apart."""
+    rows = []
+
+    def add(dtype, b, h, w, c, o, kh, kw, per_sample, k_chunks=1, shuffle=0):                # stride 1, 'same' padding
+        rows.append([dtype, b, h, w, c, c, h, w, o, o, c, kh, kw, 1, 0 if shuffle else kh // 2, shuffle, per_sample, k_chunks])
+
+    for ps in (0, 1):                                                                   # the small shapes of tests/test_hip_conv.py
+        for b in (1, 2):
+            for h, w in ((8, 64), (8, 32), (7, 32), (16, 16), (15, 15), (12, 24), (32, 64), (6, 15), (3, 8)):
+                for dtype in (BF16, F32, SPLIT):
+                    add(dtype, b, h, w, 64, 64, 3, 3, ps)
+                    add(dtype, b, h, w, 64, 64, 1, 1, ps, 2)
+            add(BF16, b, 8, 8, 64, 256, 2, 2, ps, shuffle=1)
+    for b in (1, 2, 4, 8, 12, 16):                                                      # row3, per-sample: the library's own split
+        for r in (32, 64, 128, 256):
+            for c in (128, 256, 512):
+                add(BF16, b, r, r, c, c, 3, 3, 1)
+    for c, o in ((64, 64), (128, 128), (128, 256), (256, 768), (896, 896), (1024, 512)):     # slice-per-XCD order: <= 6 channel tiles
+        for b in (1, 3, 16):
+            for r in (8, 16, 48):
+                add(BF16, b, r, r, c, o, 3, 3, 0)
+                add(BF16, b, r, r, c, o, 3, 3, 1, 8)
+    for b in (7, 8, 15, 16, 31, 32):                                                    # row3's 2 GiB rule: gy / x of the batch behind one descriptor
+        add(BF16, b, 512, 512, 256, 256, 3, 3, 0)
+        add(BF16, b, 1024, 512, 64, 64, 3, 3, 0)
+    add(BF16, 1 << 20, 64, 64, 64, 64, 3, 3, 1, 32)                                      # refused: more than 2^24 K-slices
+    add(BF16, 70000, 4, 4, 64, 64, 1, 1, 1, 1024)
+    add(7, 16, 64, 64, 64, 64, 3, 3, 0)                                                 # refused: no such dtype
+    add(BF16, 16, 64, 64, 60, 64, 3, 3, 0)                                              # refused: channel stride not a multiple of 16 bytes
+    add(BF16, 16, 64, 64, 64, 64, 3, 3, 0, 0)                                           # invalid: k_chunks 0
+    return rows
+
+
+def wgrad_plan_rows():
+    return wgrad_rows() + wgrad_plan_extra_rows()
+
+
+def wgrad_plan(lib, row):
+    """msg_conv2d_wgrad_plan's answer for a row: the MSG_WPLAN_FIELDS fields, or its negative code."""
+    import ctypes
+    out = (ctypes.c_longlong * 11)()
+    rc = lib.msg_conv2d_wgrad_plan(*row, ctypes.addressof(out), 11)
+    return list(out) if rc == 0 else rc
+
+
 ROWS = {"plan": plan_rows, "upconv_eligible": upconv_rows, "thin_eligible": thin_rows, "wgrad_workspace": wgrad_rows}
+# every table of the file: the four above as they always were (a reader that knows only them still finds each of its digests), and
+# the weight-gradient plans
+ALL_ROWS = {**ROWS, "wgrad_plan": wgrad_plan_rows}
 
 
 def digest(rows):
@@ -259,7 +303,7 @@ def digest(rows):
 
 
 def evaluate(lib):
-    """{table name: the answers, one per row of ROWS[name]()}.  plan: [MSG_PLAN_* code, msg_conv2d_fprop_act_backward_workspace
+    """{table name: the answers, one per row of ALL_ROWS[name]()}.  plan: [MSG_PLAN_* code, msg_conv2d_fprop_act_backward_workspace
     without and with noise] (the code alone where both are 0)."""
     out = {}
     out["plan"] = []
@@ -270,6 +314,7 @@ def evaluate(lib):
     out["upconv_eligible"] = [lib.msg_conv2d_fprop_upconv_eligible(*r) for r in upconv_rows()]
     out["thin_eligible"] = [lib.msg_conv2d_fprop_thin_eligible(*r) for r in thin_rows()]
     out["wgrad_workspace"] = [lib.msg_conv2d_wgrad_workspace(*r) for r in wgrad_rows()]
+    out["wgrad_plan"] = [wgrad_plan(lib, r) for r in wgrad_plan_rows()]
     return out
 
 
@@ -280,14 +325,20 @@ def main():
     sys.path.insert(0, root)
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(root, "tests", "golden", "dispatch_table.json"))
+    ap.add_argument("--only", action="append", choices=sorted(ALL_ROWS), help="record this table alone (repeatable); the others keep "
+                    "the answers the file holds -- how a NEW table is recorded without re-recording the reference of the rest")
     a = ap.parse_args()
     from multi_stylegan_amd import _lib
     from multi_stylegan_amd.build import build
     build(verbose=False)
     tables = evaluate(_lib.lib())
+    if a.only:
+        with open(a.out) as f:
+            kept = json.load(f)
+        tables = {k: v if k in a.only else kept[k] for k, v in tables.items()}
     with open(a.out, "w") as f:
-        f.write('{\n "rows": "tools/gen_dispatch_table.py: ROWS[name]() gives the arguments, in this order; digest = of those rows",\n')
-        f.write(' "digest": ' + json.dumps({k: digest(fn()) for k, fn in ROWS.items()}))
+        f.write('{\n "rows": "tools/gen_dispatch_table.py: ALL_ROWS[name]() gives the arguments, in this order; digest = of those rows",\n')
+        f.write(' "digest": ' + json.dumps({k: digest(fn()) for k, fn in ALL_ROWS.items()}))
         for k, v in tables.items():
             body = textwrap.fill(json.dumps(v, separators=(",", ":")).replace(",", ", "), 180).replace(", ", ",")
             f.write(f',\n "{k}": ' + body.replace("\n", "\n  "))
