@@ -428,8 +428,9 @@ int msg_conv2d_fprop_act(const void* x, const void* w, void* y, int dtype,
                          int noise_batch, float alpha, float scale, void* stream);
 /* ... which also leaves the sign bytes of its output (see msg_upfirdn2d_separable_act_mask): mask, B * OH * OW * N / 8 bytes
  * in the order of the kernel's output tiles (256 pixels x 256 channels for MSG_PLAN_ROW3, 128 x 128 for MSG_PLAN_ROW3N: the
- * tile_m / tile_n of msg_bias_act_backward_mask), or NULL.  Only the row-sharing 3x3 kernels write them (msg_conv2d_fprop_plan(...)
- * is MSG_PLAN_ROW3 or MSG_PLAN_ROW3N, bf16): any other problem with mask != NULL is MSG_EUNSUPPORTED -- ask the plan first. */
+ * tile_m / tile_n of msg_bias_act_backward_mask), or NULL.  Only the row-sharing 3x3 kernels write them (msg_conv2d_fprop_launch_plan
+ * with these arguments at epilogue 1 is MSG_PLAN_ROW3 or MSG_PLAN_ROW3N): any other problem with mask != NULL is MSG_EUNSUPPORTED
+ * -- ask the plan first. */
 int msg_conv2d_fprop_act_mask(const void* x, const void* w, void* y, int dtype,
                               int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                               int kh, int kw, int stride, int pad, long long w_batch_stride,
@@ -454,11 +455,9 @@ int msg_conv2d_fprop_residual(const void* x, const void* w, void* y, int dtype,
  * mask_tile_m x mask_tile_n with mask_tile_m 1 or a multiple of 64, mask_tile_n a multiple of 128) or by `sign_map` (that output itself, bf16, channel pitch
  * sign_ld) -- exactly one of the two.  residual: a second gradient of the same map (added first), or NULL.  noise [noise_batch]
  * [OH*OW] fp32 with grad_noise_weight, or both NULL.  Sums: fp32, overwritten, deterministic (per-tile partials in `ws`, summed in
- * index order; ws_floats >= msg_conv2d_fprop_act_backward_workspace(...)).  Only the row-sharing kernels have this epilogue:
- * MSG_EUNSUPPORTED unless msg_conv2d_fprop_plan(...) is MSG_PLAN_ROW3 or MSG_PLAN_ROW3N (the workspace query then returns 0),
- * bf16, ldy == N. */
-long long msg_conv2d_fprop_act_backward_workspace(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW,
-                                                  int N, int kh, int kw, long long w_batch_stride, int has_noise);
+ * index order).  Ask msg_conv2d_fprop_launch_plan with these arguments at epilogue 3 first: ws_floats >= act_rows * N floats with
+ * grad_bias, + act_entries with noise.  Only the row-sharing kernels have this epilogue, for a dense output (ldy == N):
+ * MSG_EUNSUPPORTED where the plan gives act_rows = 0. */
 int msg_conv2d_fprop_act_backward(const void* x, const void* w, void* y, int dtype,
                                   int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                                   int kh, int kw, int stride, int pad, long long w_batch_stride,
@@ -512,17 +511,32 @@ int msg_linear_grouped_wgrad(const float* gy, const float* x, const int* slot, f
 int msg_linear_grouped_wgrad_ptrs(const float* gy, const float* x, const int* slot, float* const* gw, float* const* gb, int G,
                                   int M, int N, int K, int L, float gain, float bias_gain, void* stream);
 
-/* Which kernel msg_conv2d_fprop launches for a problem (no launch).  Used by bench.py to label per-kernel timings. */
+/* What a forward convolution or data gradient launches for a problem (no launch): the geometry arguments of msg_conv2d_fprop --
+ * those of the launch in question, its real ldy, stride and padding --, whether it has a bias, and its epilogue: 0 plain
+ * (msg_conv2d_fprop), 1 the fused activation (msg_conv2d_fprop_act / _act_mask), 2 the residual merge (msg_conv2d_fprop_residual),
+ * 3 the activation backward in a data gradient (msg_conv2d_fprop_act_backward); 1 .. 3 have no bias, in_up or pixel_shuffle.
+ * `out` receives the first min(n_out_fields, MSG_FPLAN_FIELDS) of
+ *   [0] kernel              a MSG_PLAN_* code
+ *   [1] tile_m  [2] tile_n  the kernel's output tile, pixels x channels (0: the streaming kernels); with MSG_PLAN_ROW3 / ROW3N
+ *                           the tile of the sign bytes msg_conv2d_fprop_act_mask leaves (no other kernel writes them)
+ *   [3] act_rows  [4] act_entries   epilogue 3 on a row-sharing kernel: the partial-sum rows ([N] floats each) and noise entries
+ *                           of msg_conv2d_fprop_act_backward; else 0 -- at epilogue 3 that launch is then MSG_EUNSUPPORTED
+ * Returns MSG_OK, or the MSG_E* code the launch returns for the geometry before it looks at a pointer (`out` is then left alone).
+ * B = 0: MSG_OK and all fields 0.  This is the selection the launches themselves go through: timing labels, the sign-byte gate,
+ * workspace sizes and tests ask it, and nothing else. */
 enum {
     MSG_PLAN_REG = 0,   /* 128x128 tile, register staging */
     MSG_PLAN_DMA = 1,   /* 128x128 tile, LDS-DMA staging */
     MSG_PLAN_PP = 2,    /* 256x256 ping-pong */
     MSG_PLAN_ROW3 = 3,  /* 3x3 row-sharing kernel, 256x256 tile */
     MSG_PLAN_ROW3N = 4, /* 3x3 row-sharing kernel, 128x128 tile */
-    MSG_PLAN_THIN = 5   /* the streaming kernels for 1x1 convolutions with <= 8 channels on one side (conv_thin.hip) */
+    MSG_PLAN_THIN = 5,  /* the streaming kernels for 1x1 convolutions with <= 8 channels on one side (conv_thin.hip) */
+    MSG_PLAN_UPCONV = 6, /* the activation-stationary sub-pixel up-convolution (conv_upconv.hip) */
+    MSG_FPLAN_FIELDS = 5
 };
-int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
-                          int kh, int kw, long long w_batch_stride);
+int msg_conv2d_fprop_launch_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
+                                 int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
+                                 long long w_batch_stride, int has_bias, int epilogue, long long* out, int n_out_fields);
 /* What msg_conv2d_wgrad launches for a problem (no launch): the arguments of msg_conv2d_wgrad_workspace, and `out` receives the
  * first min(n_out_fields, MSG_WPLAN_FIELDS) of
  *   [0] kernel          a MSG_WPLAN_* code
@@ -547,14 +561,20 @@ enum {
 int msg_conv2d_wgrad_plan(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy,
                           int O, int ldgw, int kh, int kw, int stride, int pad, int pixel_shuffle,
                           int per_sample, int k_chunks, long long* out, int n_out_fields);
-/* 1 if msg_conv2d_fprop takes this problem to the activation-stationary sub-pixel up-convolution kernel (conv_upconv.hip:
- * K = 512, N = 4 * 512, per-sample weights, pixel-shuffled output, bf16), else 0.  For timing labels. */
+/* The four queries from before msg_conv2d_fprop_launch_plan, kept until the next ABI version: each is that query for the problem
+ * it ASSUMES around the arguments it has, without the argument checks (so never an MSG_E* code).
+ *   msg_conv2d_fprop_plan: stride 1, the 'same' padding kh / 2, no in_up, no pixel shuffle, ldy = N rounded up to 8, no bias,
+ *     epilogue 0; returns the MSG_PLAN_* code (a pixel shuffle is needed for MSG_PLAN_UPCONV: never returned).
+ *   msg_conv2d_fprop_act_backward_workspace: the same problem at epilogue 3; act_rows * N (+ act_entries with has_noise) floats.
+ *   msg_conv2d_fprop_upconv_eligible: bf16, ldy = N / 4, no bias, epilogue 0; 1 for MSG_PLAN_UPCONV, else 0.
+ *   msg_conv2d_fprop_thin_eligible: bf16, one weight set for the batch, no bias, epilogue act_mode (0 .. 2); for MSG_PLAN_THIN
+ *     1 (N <= 8 output channels) or 2 (an 8-channel-padded input), else 0. */
+int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
+                          int kh, int kw, long long w_batch_stride);
+long long msg_conv2d_fprop_act_backward_workspace(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW,
+                                                  int N, int kh, int kw, long long w_batch_stride, int has_noise);
 int msg_conv2d_fprop_upconv_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
                                      int stride, int pad, int in_up, int pixel_shuffle, long long w_batch_stride);
-/* 1 / 2 if msg_conv2d_fprop takes this bf16 problem to the streaming kernels of conv_thin.hip -- a 1x1 convolution to N <= 8
- * output channels (1: the RGB heads multi_stylegan_generator.py:472-526, the pixel-wise head u_net_2d_discriminator.py:93-97)
- * or from an 8-channel-padded input (2: their data gradients, the first block's residual conv) -- else 0.  act_mode: 0 = plain /
- * bias, 1 = fused activation, 2 = residual merge (as msg_conv2d_fprop_act / _residual).  For timing labels and tests. */
 int msg_conv2d_fprop_thin_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy, int kh, int kw,
                                    int stride, int pad, int in_up, int pixel_shuffle, int act_mode);
 

@@ -19,6 +19,8 @@ kernel-side images are built by one kernel per parameter and cached until that p
 (_ConvActF, _ModulatedConv with fuse_act), conv + residual merge (_ConvResidualF).
 There is no CPU or library fallback.
 """
+import ctypes
+import functools
 import math
 import os
 from typing import Optional, Tuple
@@ -437,12 +439,26 @@ def _contraction_code(t: torch.Tensor, mode: Optional[str] = None) -> int:
     return _SPLIT_CODES[mode] if (code == _lib.MSG_F32 and mode != "exact") else code
 
 
-# msg_conv2d_fprop_plan's kernel -> (its kernel-clock label, the output tile its activation epilogue leaves sign bytes in: only
-# the row-sharing 3x3 kernels write them)
+# MSG_PLAN_* kernel -> (its kernel-clock label, the output tile its activation epilogue leaves sign bytes in: only the row-sharing
+# 3x3 kernels write them)
 _PLANS = {_lib.MSG_PLAN_REG: ("conv_fprop_reg", None), _lib.MSG_PLAN_DMA: ("conv_fprop_dma", None),
           _lib.MSG_PLAN_PP: ("conv_fprop_pp", None), _lib.MSG_PLAN_ROW3: ("conv_fprop_row3", 256),
-          _lib.MSG_PLAN_ROW3N: ("conv_fprop_row3n", 128), _lib.MSG_PLAN_THIN: ("conv_fprop_thin", None)}
-_PLAN_CACHE: dict = {}
+          _lib.MSG_PLAN_ROW3N: ("conv_fprop_row3n", 128), _lib.MSG_PLAN_THIN: ("conv_fprop_thin", None),
+          _lib.MSG_PLAN_UPCONV: ("conv_fprop_upconv", None)}
+
+
+@functools.lru_cache(maxsize=None)
+def _fprop_plan(*args):
+    """What the library runs for a launch of the forward family: msg_conv2d_fprop_launch_plan(*args) -- dtype .. w_batch_stride as
+    the launch gets them, has_bias, epilogue (0 plain, 1 activation, 2 residual, 3 activation backward) -- asked once per tuple.
+    -> (kernel, its clock label, the tile of its sign bytes | None, floats of the activation backward's bias rows, ... of its
+    noise entries).  A geometry the library refuses has no kernel: the launch reports the code."""
+    out = (ctypes.c_longlong * _lib.MSG_FPLAN_FIELDS)()
+    ok = _lib.lib().msg_conv2d_fprop_launch_plan(*args, ctypes.addressof(out), len(out)) == _lib.MSG_OK
+    kernel = out[0] if ok else None
+    return (kernel,) + _PLANS.get(kernel, ("conv_fprop", None)) + (out[3] * args[8], out[4])
+
+
 _WGRAD_WS_CACHE: dict = {}
 
 
@@ -478,17 +494,17 @@ def _launch_fprop(x, wk, ck, bias, n, out_hw, kh, kw, stride, pad, in_up, pixel_
     # algorithmic FLOPs: real channels, and only the taps a transposed strided conv can reach (1/in_up^2)
     if flops is None:
         flops = 2.0 * b * oh * ow * n * kh * kw * c_real / (in_up * in_up)
-    key = "conv_fprop"
-    if _lib.kernel_clock.enabled:                       # label the timing with the kernel the library will pick
-        plan = _lib.lib().msg_conv2d_fprop_plan(_lib.dtype_code(x), b, ih, iw, cx, ck, oh, ow, n, kh, kw, wstride)
-        key = _PLANS[_lib.MSG_PLAN_REG if plan == _lib.MSG_PLAN_THIN and act is not None else plan][0]
-        if x.dtype == torch.bfloat16 and bias is None and act is None and residual is None and \
-                _lib.lib().msg_conv2d_fprop_upconv_eligible(b, ih, iw, cx, ck, oh, ow, n, kh, kw, stride, pad, in_up,
-                                                           int(pixel_shuffle), wstride):
-            key = "conv_fprop_upconv"
-        if _CLOCK_SHAPES:
-            key += f"|B{b} {ih}x{iw}->{oh}x{ow} {c_real}->{n} {kh}x{kw} s{stride} up{in_up}" \
-                   f"{' ps' if pixel_shuffle else ''}{' per-sample' if per_sample else ''}|"
+    key, sign_tile = "conv_fprop", None
+    # act[5]: a list that receives the sign bytes of the output -- (bytes, tile_m, tile_n), the kernel's output tile -- when the
+    # kernel this problem goes to writes them
+    sign_holder = act[5] if act is not None and len(act) > 5 else None
+    if _lib.kernel_clock.enabled or sign_holder is not None:     # (asked with the storage code: fp32 labels do not tell the split products apart)
+        _, key, sign_tile, _, _ = _fprop_plan(_lib.dtype_code(x), b, ih, iw, cx, ck, oh, ow, n, ldy, kh, kw, stride, pad, in_up,
+                                              int(pixel_shuffle), wstride, int(bias is not None),
+                                              2 if residual is not None else int(act is not None))
+    if _lib.kernel_clock.enabled and _CLOCK_SHAPES:     # (key: the timing's label -- the kernel the library will pick)
+        key += f"|B{b} {ih}x{iw}->{oh}x{ow} {c_real}->{n} {kh}x{kw} s{stride} up{in_up}" \
+               f"{' ps' if pixel_shuffle else ''}{' per-sample' if per_sample else ''}|"
     with _lib.on_device(dev), _lib.kernel_clock.span((key, 'bf16' if x.dtype == torch.bfloat16 else 'f32'), flops):
         if residual is not None:
             assert bias is None and act is None and in_up == 1 and not pixel_shuffle
@@ -506,20 +522,11 @@ def _launch_fprop(x, wk, ck, bias, n, out_hw, kh, kw, stride, pad, in_up, pixel_
             act_bias, noise, noise_w, alpha, scale = act[:5]
             _lib.require_gpu(x, act_bias, noise, noise_w)
             mask = None
-            if len(act) > 5 and act[5] is not None and kh == 3 and stride == 1 and pad == 1:
-                # (act[5]: a list that receives the sign bytes of the output -- (bytes, tile_m, tile_n), the kernel's output
-                #  tile -- when the kernel this problem goes to writes them)
-                pkey = (x.dtype, b, ih, iw, cx, ck, oh, ow, n, kh, kw, wstride)
-                mplan = _PLAN_CACHE.get(pkey)
-                if mplan is None:          # (the library's kernel choice is a pure function of the geometry: asked once)
-                    mplan = _PLAN_CACHE[pkey] = _lib.lib().msg_conv2d_fprop_plan(_lib.dtype_code(x), b, ih, iw, cx, ck, oh, ow,
-                                                                                n, kh, kw, wstride)
-                tile = _PLANS[mplan][1]
-                if tile:
-                    from .op_static.fused_act import sign_mask_for
-                    mask = sign_mask_for(b, n, oh, ow, x.dtype, dev)
-                    if mask is not None:
-                        act[5].append((mask, tile, tile))
+            if sign_holder is not None and sign_tile:
+                from .op_static.fused_act import sign_mask_for
+                mask = sign_mask_for(b, n, oh, ow, x.dtype, dev)
+                if mask is not None:
+                    sign_holder.append((mask, sign_tile, sign_tile))
             code = _lib.lib().msg_conv2d_fprop_act_mask(
                 xv.data_ptr(), wk.data_ptr(), y.data_ptr(), _contraction_code(x, mode), b, ih, iw, cx, ck, oh, ow, n, ldy, kh, kw,
                 stride, pad, wstride, _lib.ptr(act_bias), _lib.ptr(noise), _lib.ptr(noise_w),
@@ -729,15 +736,13 @@ class ActHandle:
         self.armed, self.done = True, None
 
 
-_ACTBWD_WS_CACHE: dict = {}
-
-
 def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle: ActHandle, residual=None, mode=None,
                                sign_map=None):
     """The data-gradient contraction (a 3x3 'same' conv of gy with the data-gradient weight image) with the backward of the
     activation stage described by `handle` in its epilogue.  Returns the masked gradient and fills handle.done = (grad_bias,
-    grad_noise_weight), or returns None when the library declines (another kernel would run this problem, odd layouts)."""
-    if torch.is_grad_enabled() or gy.dtype != torch.bfloat16 or kh != 3 or kw != 3 or n % 8:
+    grad_noise_weight), or returns None when the library has no such launch for the problem (its plan: another kernel would run
+    it) or the operands are laid out otherwise."""
+    if torch.is_grad_enabled() or gy.dtype != torch.bfloat16:
         return None
     if mode is not None and _contraction_code(gy, mode) != _lib.MSG_BF16:
         return None
@@ -746,13 +751,11 @@ def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle
     b, _, h, w_ = xv.shape
     wstride = wk.stride(0) if per_sample else 0
     noise = handle.noise
-    wkey = (b, h, w_, cx, ck, n, wstride, noise is not None)
-    need = _ACTBWD_WS_CACHE.get(wkey)
-    if need is None:
-        need = _ACTBWD_WS_CACHE[wkey] = _lib.lib().msg_conv2d_fprop_act_backward_workspace(
-            _lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, kh, kw, wstride, int(noise is not None))
-    if not need:
+    ldy = _round_up(n, _vec(gy.dtype))                  # (what _alloc_out gives the result)
+    _, label, _, bias_floats, noise_floats = _fprop_plan(_lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, ldy, kh, kw, 1, 1, 1, 0, wstride, 0, 3)
+    if not bias_floats:
         return None
+    need = bias_floats + (noise_floats if noise is not None else 0)
     sign = handle.sign
     smask = smap = None
     tm = tn = sld = 0
@@ -789,9 +792,7 @@ def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle
         gnw = torch.empty(1, dtype=torch.float32, device=dev)
     ws = _lib.scratch_ptr(need, dev)
     flops = 2.0 * b * h * w_ * n * kh * kw * c_real
-    key = "conv_fprop_row3_actbwd"
-    if _lib.kernel_clock.enabled:                       # (the 256 x 256 tile -- the benchmark's roofline kernel -- or the 128 x 128 one)
-        key = _PLANS[_lib.lib().msg_conv2d_fprop_plan(_lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, kh, kw, wstride)][0] + "_actbwd"
+    key = label + "_actbwd"                             # (the 256 x 256 tile -- the benchmark's roofline kernel -- or the 128 x 128 one)
     if _lib.kernel_clock.enabled and _CLOCK_SHAPES:
         key += f"|B{b} {h}x{w_}->{h}x{w_} {c_real}->{n} 3x3 s1 up1{' per-sample' if per_sample else ''}|"
     with _lib.on_device(dev), _lib.kernel_clock.span((key, 'bf16'), flops):
@@ -799,9 +800,6 @@ def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle
             xv.data_ptr(), wk.data_ptr(), y.data_ptr(), _lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, ldy, kh, kw, 1, 1, wstride,
             _lib.ptr(rv), res_ld, _lib.ptr(smask), tm, tn, _lib.ptr(smap), sld, handle.alpha, handle.scale,
             _lib.ptr(gb), _lib.ptr(nz), nb, _lib.ptr(gnw), ws, need, _lib.stream_of(dev))
-    if code == _lib.MSG_EUNSUPPORTED:
-        _ACTBWD_WS_CACHE[wkey] = 0          # (not asked again for this geometry)
-        return None
     _lib.check(code, "msg_conv2d_fprop_act_backward")
     handle.done = (gb, gnw)
     return y

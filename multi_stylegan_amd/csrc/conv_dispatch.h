@@ -6,8 +6,8 @@
 // Forward convolutions and data gradients (msg_conv2d_fprop*): conv_fprop_select (conv_fprop.hip) is the only place that knows the
 // order thin, upconv, row3, pp, generic.  Each kernel file gives it `bool conv_<k>_eligible(problem, ..., ConvPlan*)` holding ALL of
 // that kernel's conditions (it fills the plan when it says yes) and `void conv_<k>_launch(problem, plan, pointers, stream)`, which
-// cannot decline.  Everything that asks "what would run" -- msg_conv2d_fprop_plan, the sign-byte gate, the activation-backward
-// workspace -- asks conv_fprop_select, i.e. the code the launch goes through.
+// cannot decline.  Every launch takes its plan from fprop_plan_for (conv_fprop.hip: the argument checks, written once, then
+// conv_fprop_select), and so does the one query, msg_conv2d_fprop_launch_plan, which has the launch's own argument list.
 // Weight gradients (msg_conv2d_wgrad*): the same shape.  conv_wgrad_select (conv_wgrad.hip) is the only place that knows the order
 // row3, generic; a WgradPlan is a value -- kernel, K split, logical rows, grid, workspace -- that the launch, the workspace query and
 // msg_conv2d_wgrad_plan all take from it.  `conv_wgrad_<k>_eligible(problem, WgradPlan*)` holds all of a kernel's conditions and

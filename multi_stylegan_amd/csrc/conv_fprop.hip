@@ -553,34 +553,135 @@ static ConvProblem conv_problem(int dtype, int B, int IH, int IW, int Cx, int Ck
     return ConvProblem{split ? (int)MSG_F32 : dtype, split, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up, pixel_shuffle,
                        w_batch_stride};
 }
-// What the queries that take the geometry alone assume about the rest: stride 1, the 'same' padding, no zero insertion, no
-// pixel shuffle, ldy = N rounded up to 8 (and, in msg_conv2d_fprop_plan, no bias and no epilogue).
-static ConvProblem conv_query_problem(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
-                                      long long w_batch_stride) {
-    return conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, N <= 8 ? 8 : (N + 7) / 8 * 8, kh, kw, 1, kh / 2, 1, 0, w_batch_stride);
+
+static ConvPlan fprop_select(const ConvProblem& q, int act_mode, bool has_bias) {
+    ActEpilogue act{};
+    act.enabled = act_mode;
+    return conv_fprop_select(q, &act, has_bias);
 }
 
-// Which kernel msg_conv2d_fprop would launch for this problem (the MSG_PLAN_* codes of msg_hip.h): THIN = the streaming kernels of
-// conv_thin.hip (1x1, <= 8 channels on one side), ROW3 / ROW3N = conv_fprop_row3_kernel<4,4> / <2,2> (3x3 'same' convs on wide
-// maps, activation tile shared by the horizontal taps; 256x256 / 128x128 tile), PP = conv_fprop_pp_kernel (256x256 ping-pong),
-// DMA = conv_fprop_kernel<T, true> (128x128, LDS-DMA staging), REG = conv_fprop_kernel<T, false> (register staging: plain, lean
-// and split-bf16).  (The up-convolution kernel needs a pixel shuffle, which this query cannot express: it has no code.)
-extern "C" int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
-                                     int kh, int kw, long long w_batch_stride) {
-    switch (conv_fprop_select(conv_query_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride), nullptr, false).kernel) {
+// The argument checks of every launch of the family, written once (MSG_OK: go on).  io: the launch's x, w, y for the null and
+// 16-byte alignment terms; nullptr for a query, which sees no pointer.
+static int fprop_check(const ConvProblem& q, const void* const* io) {
+    if (q.B < 0 || q.IH <= 0 || q.IW <= 0 || q.OH <= 0 || q.OW <= 0 || q.N <= 0 || q.kh <= 0 || q.kw <= 0 || q.stride <= 0 ||
+        q.in_up <= 0 || q.Cx <= 0 || q.Ck <= 0 || q.ldy <= 0 || (io && (!io[0] || !io[1] || !io[2])))
+        return MSG_EINVAL;
+    if (q.dtype != MSG_F32 && q.dtype != MSG_BF16) return MSG_EUNSUPPORTED;
+    const int vec = 16 / q.esz(), bke = ROWB / q.esz();      // elements per 16-byte vector / per 128-byte K run
+    if (q.Ck % bke || q.Cx % vec || (io && (((uintptr_t)io[0] | (uintptr_t)io[1] | (uintptr_t)io[2]) & 15u))) return MSG_EUNSUPPORTED;
+    if (q.ldy % vec || (q.pixel_shuffle && (q.N % 4 || (q.N / 4) % vec))) return MSG_EUNSUPPORTED;
+    if (q.in_up > 1 && q.stride != 1) return MSG_EUNSUPPORTED;
+    return MSG_OK;
+}
+
+// checks + selection: MSG_OK and the plan, or the code of a call that stops before a plan is used.  (An empty batch is MSG_OK with
+// nothing to launch: the plan is not filled.)
+static int fprop_plan_for(const ConvProblem& q, int act_mode, bool has_bias, const void* const* io, ConvPlan* plan) {
+    if (q.B == 0) return MSG_OK;
+    const int rc = fprop_check(q, io);
+    if (rc != MSG_OK) return rc;
+    *plan = fprop_select(q, act_mode, has_bias);
+    return plan->supported ? MSG_OK : MSG_EUNSUPPORTED;
+}
+
+static bool is_row3(const ConvPlan& plan) { return plan.kernel == CONV_ROW3 || plan.kernel == CONV_ROW3N; }
+
+// Partial-sum rows / entries of msg_conv2d_fprop_act_backward for a problem that `plan` sends to the row-sharing kernel: rows of
+// [N] floats (one per sample, pixel tile and wave row) and noise entries (one per sample, tile and wave); 0 rows = no fusion: the
+// problem does not go to that kernel, or its output is not dense (the epilogue's sums run over a map of pitch N).
+static void act_backward_partials(const ConvProblem& q, const ConvPlan& plan, long long* rows, long long* entries) {
+    *rows = *entries = 0;
+    if (!is_row3(plan) || q.ldy != q.N) return;
+    const long long tiles = (q.mtot() / plan.tile_m) * q.samples();
+    *rows = tiles * 2;
+    *entries = tiles * (q.N / plan.tile_n) * 4;
+}
+
+static int plan_code(ConvKernel kernel) {
+    switch (kernel) {
         case CONV_THIN_N: case CONV_THIN_K: return MSG_PLAN_THIN;
+        case CONV_UPCONV: return MSG_PLAN_UPCONV;
         case CONV_ROW3: return MSG_PLAN_ROW3;
         case CONV_ROW3N: return MSG_PLAN_ROW3N;
         case CONV_PP: return MSG_PLAN_PP;
-        case CONV_UPCONV: return MSG_PLAN_PP;      // (unreachable from this query -- no pixel shuffle; not a claim that up-conv is PP)
         case CONV_DMA: return MSG_PLAN_DMA;
         default: return MSG_PLAN_REG;
     }
 }
 
-// (selected: the plan, where the caller had to ask for it already)
+// What a launch of this family would run (no launch; the fields of MSG_FPLAN_FIELDS, msg_hip.h): the launch's own geometry
+// arguments, whether it has a bias, and its epilogue -- 0: msg_conv2d_fprop, 1: _act / _act_mask, 2: _residual, 3: _act_backward.
+extern "C" int msg_conv2d_fprop_launch_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
+                                            int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
+                                            long long w_batch_stride, int has_bias, int epilogue, long long* out, int n_out_fields) {
+    // (the launches with an epilogue have no bias, zero insertion or pixel shuffle in their argument lists)
+    if (epilogue < 0 || epilogue > 3 || (epilogue && (has_bias || in_up != 1 || pixel_shuffle))) return MSG_EINVAL;
+    const ConvProblem q = conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up, pixel_shuffle, w_batch_stride);
+    ConvPlan plan;
+    const int rc = fprop_plan_for(q, epilogue, has_bias != 0, nullptr, &plan);
+    if (rc != MSG_OK) return rc;
+    long long fields[MSG_FPLAN_FIELDS] = {};
+    if (q.B) {
+        fields[0] = plan_code(plan.kernel); fields[1] = plan.tile_m; fields[2] = plan.tile_n;
+        if (epilogue == 3) act_backward_partials(q, plan, &fields[3], &fields[4]);
+    }
+    for (int k = 0; k < MSG_FPLAN_FIELDS && k < n_out_fields; ++k) out[k] = fields[k];
+    return MSG_OK;
+}
+
+// The four queries from before msg_conv2d_fprop_launch_plan (kept for the ABI): each is the selection above for the problem it
+// ASSUMES around the arguments it has, with no argument check, and no logic of its own.
+// msg_conv2d_fprop_plan, msg_conv2d_fprop_act_backward_workspace: stride 1, the 'same' padding, no zero insertion, no pixel shuffle,
+// ldy = N rounded up to 8, no bias; no epilogue / the activation backward.
+static ConvProblem conv_query_problem(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
+                                      long long w_batch_stride) {
+    return conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, N <= 8 ? 8 : (N + 7) / 8 * 8, kh, kw, 1, kh / 2, 1, 0, w_batch_stride);
+}
+extern "C" int msg_conv2d_fprop_plan(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N,
+                                     int kh, int kw, long long w_batch_stride) {
+    return plan_code(fprop_select(conv_query_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride), 0, false).kernel);
+}
+extern "C" long long msg_conv2d_fprop_act_backward_workspace(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW,
+                                                             int N, int kh, int kw, long long w_batch_stride, int has_noise) {
+    const ConvProblem q = conv_query_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
+    long long rows, entries;
+    act_backward_partials(q, fprop_select(q, 3, false), &rows, &entries);
+    return rows ? rows * N + (has_noise ? entries : 0) : 0;
+}
+// msg_conv2d_fprop_upconv_eligible: bf16, ldy = N / 4, no bias, no epilogue
+extern "C" int msg_conv2d_fprop_upconv_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
+                                                int stride, int pad, int in_up, int pixel_shuffle, long long w_batch_stride) {
+    return fprop_select(conv_problem(MSG_BF16, B, IH, IW, Cx, Ck, OH, OW, N, N / 4, kh, kw, stride, pad, in_up, pixel_shuffle,
+                                     w_batch_stride), 0, false).kernel == CONV_UPCONV;
+}
+// msg_conv2d_fprop_thin_eligible: bf16, one weight set for the batch, no bias
+extern "C" int msg_conv2d_fprop_thin_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
+                                              int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
+                                              int act_mode) {
+    const ConvKernel kernel = fprop_select(conv_problem(MSG_BF16, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up,
+                                                        pixel_shuffle, 0), act_mode, false).kernel;
+    return kernel == CONV_THIN_N ? 1 : kernel == CONV_THIN_K ? 2 : 0;
+}
+
+// Every launch of the family: the plan of the problem, then the kernel it names.
 static int conv2d_fprop_impl(const void* x, const void* w, const float* bias, void* y, const ConvProblem& q,
-                             const ActEpilogue& act, void* stream, const ConvPlan* selected = nullptr);
+                             const ActEpilogue& act, void* stream) {
+    const void* const io[3] = {x, w, y};
+    ConvPlan plan;
+    const int rc = fprop_plan_for(q, act.enabled, bias != nullptr, io, &plan);
+    if (rc != MSG_OK || q.B == 0) return rc;
+    // only the row-sharing 3x3 kernel writes the sign bytes (the caller asks msg_conv2d_fprop_launch_plan first)
+    if (act.mask && !is_row3(plan)) return MSG_EUNSUPPORTED;
+    switch (plan.kernel) {
+        case CONV_THIN_N: case CONV_THIN_K: conv_thin_launch(q, plan, x, w, bias, y, &act, stream); break;
+        case CONV_UPCONV: conv_upconv_launch(q, plan, x, w, y, stream); break;
+        case CONV_ROW3: case CONV_ROW3N: conv_row3_launch(q, plan, x, w, bias, y, &act, stream); break;
+        case CONV_PP: conv_pp_launch(q, plan, x, w, bias, y, &act, stream); break;
+        case CONV_DMA: case CONV_REG: case CONV_REG_LEAN: case CONV_REG_SPLIT:
+            conv_generic_launch(q, plan, x, w, bias, y, &act, stream); break;
+    }
+    return MSG_CHECK_LAUNCH();
+}
 
 extern "C" int msg_conv2d_fprop(const void* x, const void* w, const float* bias, void* y, int dtype,
                                 int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
@@ -591,20 +692,15 @@ extern "C" int msg_conv2d_fprop(const void* x, const void* w, const float* bias,
                                                          pixel_shuffle, w_batch_stride), act, stream);
 }
 
-static bool is_row3(const ConvPlan& plan) { return plan.kernel == CONV_ROW3 || plan.kernel == CONV_ROW3N; }
-
 extern "C" int msg_conv2d_fprop_act_mask(const void* x, const void* w, void* y, int dtype,
                                          int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                                          int kh, int kw, int stride, int pad, long long w_batch_stride,
                                          const float* act_bias, const float* noise, const float* noise_weight,
                                          int noise_batch, float alpha, float scale, unsigned char* mask, void* stream) {
     if (noise && (!noise_weight || (noise_batch != 1 && noise_batch != B))) return MSG_EINVAL;
-    const ConvProblem q = conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0, w_batch_stride);
     ActEpilogue act{act_bias, noise, noise_weight, noise_batch, 1, alpha, scale, nullptr, 0, 0.f, mask};
-    // only the row-sharing 3x3 kernel writes the sign bytes (the caller asks msg_conv2d_fprop_plan first)
-    if (!mask) return conv2d_fprop_impl(x, w, nullptr, y, q, act, stream);
-    const ConvPlan plan = conv_fprop_select(q, &act, false);
-    return is_row3(plan) ? conv2d_fprop_impl(x, w, nullptr, y, q, act, stream, &plan) : (int)MSG_EUNSUPPORTED;
+    return conv2d_fprop_impl(x, w, nullptr, y, conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0,
+                                                            w_batch_stride), act, stream);
 }
 
 extern "C" int msg_conv2d_fprop_act(const void* x, const void* w, void* y, int dtype,
@@ -627,33 +723,13 @@ extern "C" int msg_conv2d_fprop_residual(const void* x, const void* w, void* y, 
                                                             w_batch_stride), act, stream);
 }
 
-// Partial-sum rows / entries of msg_conv2d_fprop_act_backward for a problem that `plan` sends to the row-sharing kernel: rows of
-// [N] floats (one per sample, pixel tile and wave row) and noise entries (one per sample, tile and wave); 0 rows = the problem does
-// not go to that kernel (no fusion).
-static void act_backward_partials(const ConvProblem& q, const ConvPlan& plan, long long* rows, long long* entries) {
-    *rows = *entries = 0;
-    if (!is_row3(plan)) return;
-    const long long tiles = (q.mtot() / plan.tile_m) * q.samples();
-    *rows = tiles * 2;
-    *entries = tiles * (q.N / plan.tile_n) * 4;
-}
-
-extern "C" long long msg_conv2d_fprop_act_backward_workspace(int dtype, int B, int IH, int IW, int Cx, int Ck, int OH, int OW,
-                                                             int N, int kh, int kw, long long w_batch_stride, int has_noise) {
-    const ConvProblem q = conv_query_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, kh, kw, w_batch_stride);
-    ActEpilogue act{};
-    act.enabled = 3;
-    long long rows, entries;
-    act_backward_partials(q, conv_fprop_select(q, &act, false), &rows, &entries);
-    return rows ? rows * N + (has_noise ? entries : 0) : 0;
-}
-
 // The data gradient of a 3x3 'same' conv whose INPUT was the output of a fused bias (+ noise) + leaky-ReLU stage, with that
 // stage's backward in the epilogue (ActEpilogue::enabled == 3): y = (conv(x, w) [+ residual]) * (s > 0 ? scale : scale * alpha)
 // and the stage's bias / noise-weight gradients -- the map between the two backward nodes is never written.  s: `sign_mask`
 // (bytes of msg_conv2d_fprop_act_mask / msg_upfirdn2d_separable_act_mask in tiles mask_tile_m x mask_tile_n; tile_m 1 or a
-// multiple of 64) or `sign_map` (the stage's stored output, bf16, channel pitch sign_ld).  Only the row-sharing kernels
-// (msg_conv2d_fprop_plan: MSG_PLAN_ROW3 / MSG_PLAN_ROW3N) have this epilogue: MSG_EUNSUPPORTED otherwise, as for anything but bf16.
+// multiple of 64) or `sign_map` (the stage's stored output, bf16, channel pitch sign_ld).  Only the row-sharing kernels, writing
+// a dense map (ldy == N), have this epilogue -- msg_conv2d_fprop_launch_plan at epilogue 3 then gives the partial-sum rows --:
+// MSG_EUNSUPPORTED otherwise.
 extern "C" int msg_conv2d_fprop_act_backward(const void* x, const void* w, void* y, int dtype,
                                              int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                                              int kh, int kw, int stride, int pad, long long w_batch_stride,
@@ -663,13 +739,12 @@ extern "C" int msg_conv2d_fprop_act_backward(const void* x, const void* w, void*
                                              float* grad_bias, const float* noise, int noise_batch, float* grad_noise_weight,
                                              float* ws, long long ws_floats, void* stream) {
     if (B == 0) return MSG_OK;
-    if (!x || !w || !y || B < 0) return MSG_EINVAL;
     if (!sign_mask == !sign_map) return MSG_EINVAL;                         // exactly one sign source
-    if (stride != 1 || pad != 1 || kh != 3 || kw != 3 || ldy != N) return MSG_EUNSUPPORTED;
     const ConvProblem q = conv_problem(dtype, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, 1, 0, w_batch_stride);
-    ActEpilogue act{};
-    act.enabled = 3; act.alpha = alpha; act.scale = scale;
-    const ConvPlan plan = conv_fprop_select(q, &act, false);
+    const void* const io[3] = {x, w, y};
+    ConvPlan plan;
+    const int rc = fprop_plan_for(q, 3, false, io, &plan);
+    if (rc != MSG_OK) return rc;
     long long rows, entries;
     act_backward_partials(q, plan, &rows, &entries);
     if (!rows) return MSG_EUNSUPPORTED;
@@ -682,6 +757,8 @@ extern "C" int msg_conv2d_fprop_act_backward(const void* x, const void* w, void*
     if (has_noise && noise_batch != 1 && noise_batch != B) return MSG_EINVAL;
     const long long need_b = grad_bias ? rows * N : 0, need_n = has_noise ? entries : 0;
     if (need_b + need_n > 0 && (!ws || ws_floats < need_b + need_n)) return MSG_EINVAL;
+    ActEpilogue act{};
+    act.enabled = 3; act.alpha = alpha; act.scale = scale;
     act.residual = residual; act.res_ld = res_ld; act.res_gain = 1.f;
     act.mask = const_cast<unsigned char*>(sign_mask); act.mask_tile_m = mask_tile_m; act.mask_tile_n = mask_tile_n;
     act.sign_src = sign_map; act.sign_ld = sign_ld;
@@ -691,28 +768,4 @@ extern "C" int msg_conv2d_fprop_act_backward(const void* x, const void* w, void*
     conv_row3_launch(q, plan, x, w, nullptr, y, &act, stream);
     if (MSG_CHECK_LAUNCH() != MSG_OK) return MSG_ELAUNCH;
     return msg_bias_act_reduce_launch(act.part_b, grad_bias, N, rows, act.part_n, grad_noise_weight, entries, stream);
-}
-
-static int conv2d_fprop_impl(const void* x, const void* w, const float* bias, void* y, const ConvProblem& q,
-                             const ActEpilogue& act, void* stream, const ConvPlan* selected) {
-    if (q.B == 0) return MSG_OK;
-    if (!x || !w || !y || q.B < 0 || q.IH <= 0 || q.IW <= 0 || q.OH <= 0 || q.OW <= 0 || q.N <= 0 || q.kh <= 0 || q.kw <= 0 ||
-        q.stride <= 0 || q.in_up <= 0 || q.Cx <= 0 || q.Ck <= 0 || q.ldy <= 0)
-        return MSG_EINVAL;
-    if (q.dtype != MSG_F32 && q.dtype != MSG_BF16) return MSG_EUNSUPPORTED;
-    const int vec = 16 / q.esz(), bke = ROWB / q.esz();      // elements per 16-byte vector / per 128-byte K run
-    if (q.Ck % bke || q.Cx % vec || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15u)) return MSG_EUNSUPPORTED;
-    if (q.ldy % vec || (q.pixel_shuffle && (q.N % 4 || (q.N / 4) % vec))) return MSG_EUNSUPPORTED;
-    if (q.in_up > 1 && q.stride != 1) return MSG_EUNSUPPORTED;
-    const ConvPlan plan = selected ? *selected : conv_fprop_select(q, &act, bias != nullptr);
-    if (!plan.supported) return MSG_EUNSUPPORTED;
-    switch (plan.kernel) {
-        case CONV_THIN_N: case CONV_THIN_K: conv_thin_launch(q, plan, x, w, bias, y, &act, stream); break;
-        case CONV_UPCONV: conv_upconv_launch(q, plan, x, w, y, stream); break;
-        case CONV_ROW3: case CONV_ROW3N: conv_row3_launch(q, plan, x, w, bias, y, &act, stream); break;
-        case CONV_PP: conv_pp_launch(q, plan, x, w, bias, y, &act, stream); break;
-        case CONV_DMA: case CONV_REG: case CONV_REG_LEAN: case CONV_REG_SPLIT:
-            conv_generic_launch(q, plan, x, w, bias, y, &act, stream); break;
-    }
-    return MSG_CHECK_LAUNCH();
 }

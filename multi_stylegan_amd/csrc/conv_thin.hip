@@ -266,17 +266,6 @@ bool conv_thin_eligible(const ConvProblem& q, const ActEpilogue* act, ConvPlan* 
     return true;
 }
 
-// (the public query has no weight stride and no dtype: shared weights, bf16)
-extern "C" int msg_conv2d_fprop_thin_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
-                                              int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
-                                              int act_mode) {
-    const ConvProblem q{MSG_BF16, 0, B, IH, IW, Cx, Ck, OH, OW, N, ldy, kh, kw, stride, pad, in_up, pixel_shuffle, 0};
-    ActEpilogue act{};
-    act.enabled = act_mode;
-    ConvPlan plan;
-    return conv_thin_eligible(q, &act, &plan) ? (plan.kernel == CONV_THIN_N ? 1 : 2) : 0;
-}
-
 void conv_thin_launch(const ConvProblem& q, const ConvPlan& plan, const void* x, const void* w, const float* bias, void* y,
                       const ActEpilogue* act, void* stream) {
     const bool per_sample = q.per_sample();

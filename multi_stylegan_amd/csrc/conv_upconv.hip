@@ -199,14 +199,6 @@ bool conv_upconv_eligible(const ConvProblem& q, const ActEpilogue* act, bool has
     return true;
 }
 
-// (the public query has no epilogue argument and no dtype: a plain bf16 launch)
-extern "C" int msg_conv2d_fprop_upconv_eligible(int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int kh, int kw,
-                                                int stride, int pad, int in_up, int pixel_shuffle, long long w_batch_stride) {
-    const ConvProblem q{MSG_BF16, 0, B, IH, IW, Cx, Ck, OH, OW, N, N / 4, kh, kw, stride, pad, in_up, pixel_shuffle, w_batch_stride};
-    ConvPlan plan;
-    return conv_upconv_eligible(q, nullptr, false, &plan);
-}
-
 void conv_upconv_launch(const ConvProblem& q, const ConvPlan&, const void* x, const void* w, void* y, void* stream) {
     UpconvParams p{};
     p.B = q.B; p.H = q.OH; p.W = q.OW; p.Cx = q.Cx; p.N = q.N; p.O = q.N / 4; p.ldy = q.ldy;

@@ -178,8 +178,50 @@ def test_round3_entries(lib):
     assert lib.msg_bias_act_backward_mask(*args[:5], F32, *args[6:]) == EUNSUPPORTED
     assert lib.msg_bias_act_backward_mask(*args[:2], 3, 64, *args[4:]) == EINVAL          # 64 pixels are not whole tiles of 3
     assert lib.msg_bias_act_backward_mask(args[0], None, *args[2:]) == EINVAL
-    # the masked conv entry refuses problems whose kernel does not write the bytes (ask msg_conv2d_fprop_plan first)
+    # the masked conv entry refuses problems whose kernel does not write the bytes (ask msg_conv2d_fprop_launch_plan first:
+    # test_masked_conv_writes_sign_bytes_exactly_where_the_plan_says)
     w = _buf(64 * 64, torch.bfloat16)
     assert lib.msg_conv2d_fprop_act_mask(xb.data_ptr(), w.data_ptr(), xb.data_ptr(), BF16, 1, 8, 8, 64, 64, 8, 8, 64, 64, 1, 1, 1, 0,
                                          0, None, None, None, 1, 0.2, 1.0, m.data_ptr(), s) == EUNSUPPORTED
     torch.cuda.synchronize()
+
+
+# One geometry per kernel a fused activation can reach, each AT that kernel's own eligibility floor (conv_<k>_eligible), B = 1:
+#   row3   3x3, 192 -> 1024 on 112 x 128: Ck above the short-K rule (128), 56 x 4 = 224 tiles of 256 x 256 (the floor; 110 rows: 220)
+#   row3n  3x3, 64 -> 128 on 448 x 128: 448 tiles of 128 x 128 (the floor)
+#   pp     1x1, 256 -> 1024 on 112 x 128: 4 K-steps and 224 tiles (both floors)
+#   dma    1x1, 512 -> 128 on 32 x 32: 8 K-steps (the floor of the LDS-DMA staging), 1024 pixels
+#   reg    1x1, 448 -> 128 on 32 x 32: 7 K-steps
+_MASKED = {"row3": ("ROW3", 112, 128, 192, 1024, 3), "row3_below": ("DMA", 110, 128, 192, 1024, 3), "row3n": ("ROW3N", 448, 128, 64, 128, 3),
+           "pp": ("PP", 112, 128, 256, 1024, 1), "dma": ("DMA", 32, 32, 512, 128, 1), "reg": ("REG", 32, 32, 448, 128, 1)}
+
+
+@pytest.mark.parametrize("case", sorted(_MASKED))
+def test_masked_conv_writes_sign_bytes_exactly_where_the_plan_says(lib, case):
+    """msg_conv2d_fprop_launch_plan and msg_conv2d_fprop_act_mask answer from one selection: the plan names the kernel expected for
+    the shape, and the masked launch is MSG_OK with bytes equal to the sign of the stored output exactly when the plan names a
+    sign-byte tile (the row-sharing kernels) -- otherwise MSG_EUNSUPPORTED, and nothing is launched (the output keeps its
+    contents)."""
+    from multi_stylegan_amd import _lib, conv_ops
+    kernel, h, w_, c, n, k = _MASKED[case]
+    gen = torch.Generator(device=DEV).manual_seed(5)
+    x = torch.randn(h * w_ * c, device=DEV, generator=gen).to(torch.bfloat16)
+    w = (torch.randn(n * k * k * c, device=DEV, generator=gen) * 0.05).to(torch.bfloat16)
+    y = torch.full((h * w_, n), 7.0, device=DEV, dtype=torch.bfloat16)
+    mask = torch.zeros(h * w_ * n // 8, device=DEV, dtype=torch.uint8)
+    geom = (BF16, 1, h, w_, c, c, h, w_, n, n, k, k, 1, k // 2)
+    out = (ctypes.c_longlong * _lib.MSG_FPLAN_FIELDS)()
+    assert lib.msg_conv2d_fprop_launch_plan(*geom, 1, 0, 0, 0, 1, ctypes.addressof(out), len(out)) == OK
+    assert out[0] == getattr(_lib, "MSG_PLAN_" + kernel), (case, list(out))
+    tile = conv_ops._PLANS[out[0]][1]
+    assert (tile is not None) == kernel.startswith("ROW3") and (tile is None or (out[1], out[2]) == (tile, tile))
+    code = lib.msg_conv2d_fprop_act_mask(x.data_ptr(), w.data_ptr(), y.data_ptr(), *geom, 0, None, None, None, 1, 0.2, 1.0,
+                                         mask.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    if tile is None:
+        assert code == EUNSUPPORTED and bool((y == 7.0).all()) and not bool(mask.any())
+        return
+    assert code == OK
+    bits = (y > 0).view(h * w_ // tile, tile, n // tile, tile // 8, 8).permute(0, 2, 1, 3, 4)      # act_mask_index: tile after tile
+    want = (bits.to(torch.int32) << torch.arange(8, device=DEV, dtype=torch.int32)).sum(-1).to(torch.uint8).reshape(-1)
+    assert 0.25 < float((y > 0).float().mean()) < 0.75 and torch.equal(mask, want)

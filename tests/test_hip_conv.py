@@ -821,7 +821,8 @@ def test_activation_stationary_upconv_kernel(batch, hw):
     w = (torch.randn(batch, o, i, 2, 2, device=DEV) / math.sqrt(i)).bfloat16().float()
     geo = conv_ops.Geometry("up2", 2, 2, 1, 0, (h, w_), True)
     wk, ck = conv_ops._relay_fwd_kind(w, torch.bfloat16, "up2")
-    assert _lib.lib().msg_conv2d_fprop_upconv_eligible(batch, h, w_, i, ck, h, w_, 4 * o, 1, 1, 1, 0, 1, 1, wk.stride(0)) == 1
+    assert conv_ops._fprop_plan(_lib.MSG_BF16, batch, h, w_, i, ck, h, w_, 4 * o, o, 1, 1, 1, 0, 1, 1, wk.stride(0), 0,
+                                0)[0] == _lib.MSG_PLAN_UPCONV
     y = conv_ops._f_raw(x, w, None, geo)
     assert y.shape == (batch, o, 2 * h, 2 * w_)
     for _ in range(4):
@@ -866,9 +867,11 @@ def test_thin_pointwise_conv_kernels(case):
     geo = conv_ops.Geometry("conv", 1, 1, 1, 0, (h, w_), per_sample)
     xv, cx = conv_ops._nhwc_view(x)
     ck = 64 * ((i + 63) // 64)
-    mode = _lib.lib().msg_conv2d_fprop_thin_eligible(batch, h, w_, cx, ck, h, w_, o, 8 * ((o + 7) // 8), 1, 1, 1, 0, 1, 0,
-                                                     2 if with_res else 0)
-    assert mode == (1 if o <= 8 else 2)                                   # (the kernels under test do run)
+    wstride = o * ck if per_sample else 0
+    plan = conv_ops._fprop_plan(_lib.MSG_BF16, batch, h, w_, cx, ck, h, w_, o, 8 * ((o + 7) // 8), 1, 1, 1, 0, 1, 0, wstride,
+                                int(with_bias), 2 if with_res else 0)
+    # (the kernels under test do run: of the two streaming kernels, the one for <= 8 output channels or the one for >= 64)
+    assert plan[0] == _lib.MSG_PLAN_THIN and (o <= 8 or o >= 64)
     res = conv_ops.to_compute_layout(torch.randn(batch, o, h, w_, device=DEV), torch.bfloat16) if with_res else None
     y = conv_ops._f_raw(x, w, bias, geo, residual=(res, 0.5) if with_res else None)
     for _ in range(3):

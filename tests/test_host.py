@@ -51,6 +51,8 @@ def test_binding_types_are_the_headers():
     assert res is I and len(args) == 22 and args[:5] == [P, P, P, P, I] and args[5:20] == [I] * 15
     assert args[20] is L and args[21] is P                                   # w_batch_stride, stream
     assert sig["msg_conv2d_fprop_plan"] == (I, [I] * 11 + [L])
+    assert sig["msg_conv2d_fprop_launch_plan"] == (I, [I] * 16 + [L, I, I, P, I])       # msg_conv2d_fprop's dtype .. w_batch_stride first
+    assert sig["msg_conv2d_fprop_launch_plan"][1][:17] == sig["msg_conv2d_fprop"][1][4:21]
     assert sig["msg_conv2d_wgrad_plan"] == (I, [I] * 18 + [P, I]) and sig["msg_conv2d_wgrad_workspace"] == (L, [I] * 18)
     assert sig["msg_flat_adam"] == (I, [P, P, P, P, P, L, P, F, F, F, F, I, F, P])
     assert sig["msg_flat_ema"] == (I, [P, P, L, F, P])
@@ -60,10 +62,11 @@ def test_binding_types_are_the_headers():
     assert (_lib.MSG_F32, _lib.MSG_BF16, _lib.MSG_F16, _lib.MSG_F64, _lib.MSG_F32_SPLIT) == (0, 1, 2, 3, 4)
     assert conv_ops.MSG_F32_SPLIT == 4
     assert (_lib.MSG_PLAN_REG, _lib.MSG_PLAN_DMA, _lib.MSG_PLAN_PP, _lib.MSG_PLAN_ROW3, _lib.MSG_PLAN_ROW3N,
-            _lib.MSG_PLAN_THIN) == (0, 1, 2, 3, 4, 5)
+            _lib.MSG_PLAN_THIN, _lib.MSG_PLAN_UPCONV, _lib.MSG_FPLAN_FIELDS) == (0, 1, 2, 3, 4, 5, 6, 5)
     # the kernel-clock labels bench.py, profiles/ and the tools key on, and the tile of the sign bytes, per plan
     assert conv_ops._PLANS == {0: ("conv_fprop_reg", None), 1: ("conv_fprop_dma", None), 2: ("conv_fprop_pp", None),
-                               3: ("conv_fprop_row3", 256), 4: ("conv_fprop_row3n", 128), 5: ("conv_fprop_thin", None)}
+                               3: ("conv_fprop_row3", 256), 4: ("conv_fprop_row3n", 128), 5: ("conv_fprop_thin", None),
+                               6: ("conv_fprop_upconv", None)}
     assert _lib.ABI_VERSION == _lib.lib().msg_abi_version() == 5
     assert _lib.lib().msg_strerror(_lib.MSG_EUNSUPPORTED) != _lib.lib().msg_strerror(_lib.MSG_EINVAL)
     # every `msg_name(` of the comment-stripped header became exactly one parsed prototype
@@ -417,7 +420,8 @@ def test_kernel_plans_respect_the_31_bit_offset_limits():
 
 def test_dispatch_answers_match_the_recorded_table():
     """The host-side answers of the convolution family -- msg_conv2d_fprop_plan, msg_conv2d_fprop_act_backward_workspace,
-    msg_conv2d_fprop_upconv_eligible, msg_conv2d_fprop_thin_eligible, msg_conv2d_wgrad_workspace, msg_conv2d_wgrad_plan -- over the grid of
+    msg_conv2d_fprop_upconv_eligible, msg_conv2d_fprop_thin_eligible, msg_conv2d_wgrad_workspace, msg_conv2d_wgrad_plan,
+    msg_conv2d_fprop_launch_plan -- over the grid of
     tools/gen_dispatch_table.py (the models' geometries at 256^2 and 512^2, shared and per-sample weights, batch 1 .. 33, and both
     sides of every eligibility threshold), against tests/golden/dispatch_table.json: the answers recorded BEFORE the forward dispatch
     became one selection function.  Equality on every row, except four classes where the recorded answer named a kernel the
@@ -427,7 +431,10 @@ def test_dispatch_answers_match_the_recorded_table():
       * the up-convolution with per-sample weight sets closer than one set (stride < N * 512): eligible 1 -> 0;
       * thin with per-sample weights and more than 65535 samples (grid.y): THIN -> DMA / PP / REG, whichever tile kernel takes it.
     None of them is a geometry of the models: their thin layers have 128 / 512 channels, the Python layer asks the plan with the
-    storage code (never MSG_F32_SPLIT), per-sample weight images are dense and batches are tens of samples.  And the grid does hold
+    storage code (never MSG_F32_SPLIT), per-sample weight images are dense and batches are tens of samples.
+    msg_conv2d_fprop_launch_plan -- the launch's own arguments, bias and epilogue -- has no exceptions: its table was recorded from
+    the commit before it existed, through a query that reported that commit's conv_fprop_select, act_backward_partials and argument
+    checks, and every row must equal it.  And the grid does hold
     the models' geometries: every conv_fprop* / conv_wgrad label of the per-shape kernel tables of the benchmark has a row."""
     from multi_stylegan_amd import _lib
     from multi_stylegan_amd.build import build
@@ -445,7 +452,7 @@ def test_dispatch_answers_match_the_recorded_table():
     thin_kc = (2, 4, 6, 8, 12, 16)
     model_channels = (8, 64, 128, 256, 384, 512, 768, 1024)
     truthful = {"plan": 0, "thin_eligible": 0, "upconv_eligible": 0}
-    bad = []
+    bad, plan_codes = [], []
     for args, ans in zip(rows["plan"], table["plan"]):
         plan, ws0, ws1 = ans if isinstance(ans, list) else (ans, 0, 0)
         dtype, ck, n = args[0], args[5], args[8]
@@ -460,6 +467,7 @@ def test_dispatch_answers_match_the_recorded_table():
                lib.msg_conv2d_fprop_act_backward_workspace(*args, 1))
         if got != (plan, ws0, ws1):
             bad.append(("plan", args, (plan, ws0, ws1), got))
+        plan_codes.append((plan, ws0, ws1))
     for args, mode in zip(rows["thin_eligible"], table["thin_eligible"]):
         if mode == 1 and args[4] // 32 not in thin_kc:
             assert args[4] not in model_channels
@@ -479,7 +487,37 @@ def test_dispatch_answers_match_the_recorded_table():
     for args, ans in zip(rows["wgrad_plan"], table["wgrad_plan"]):
         if grid.wgrad_plan(lib, args) != ans:
             bad.append(("wgrad_plan", args, ans, grid.wgrad_plan(lib, args)))
+    for args, ans in zip(rows["fprop_plan"], table["fprop_plan"]):
+        if grid.fprop_plan(lib, args) != ans:
+            bad.append(("fprop_plan", args, ans, grid.fprop_plan(lib, args)))
     assert not bad, (len(bad), bad[:10])
+    # the first rows of the new table are the old plan's rows with its assumptions spelled out, at epilogue 0 without a bias: the
+    # recorded plans are the old table's codes (after the truthful classes above), unless the launch refuses the geometry -- which
+    # the old query, without the launch's checks, could not say: Ck no multiple of 128 bytes, or a K sweep beyond the zero page
+    for args, ans, (plan, _ws0, _ws1) in zip(rows["fprop_plan"], table["fprop_plan"], plan_codes):
+        bke = 64 if args[0] == bf16 else 32
+        if isinstance(ans, list):
+            assert ans[0] == plan, (args, ans, plan)
+        else:
+            assert ans == _lib.MSG_EUNSUPPORTED and (args[5] % bke or (args[10] * args[11] * (args[5] // bke) + 1) * 128 + 128 > 65536), args
+    assert [a[:9] + a[10:12] + a[16:17] for a in rows["fprop_plan"][:len(rows["plan"])]] == rows["plan"]
+    assert all(a[9:10] + a[12:16] + a[17:] == [max(8, (a[8] + 7) // 8 * 8), 1, a[10] // 2, 1, 0, 0, 0] for a in rows["fprop_plan"][:len(rows["plan"])])
+    # ... and, under the same assumptions at epilogue 3, the old workspace query is act_rows * N (+ act_entries with noise)
+    fplans = dict(zip(map(tuple, rows["fprop_plan"]), table["fprop_plan"]))
+    for key, ans in fplans.items():
+        if key[18] == 3 and isinstance(ans, list) and (key[9], key[12:16]) == (max(8, (key[8] + 7) // 8 * 8), (1, key[10] // 2, 1, 0)):
+            act_rows, act_entries = (ans + [0, 0])[3:5]
+            old = [lib.msg_conv2d_fprop_act_backward_workspace(*key[:9], *key[10:12], key[16], noise) for noise in (0, 1)]
+            assert old == ([act_rows * key[8], act_rows * key[8] + act_entries] if act_rows else [0, 0]), (key, ans, old)
+    # what the new table holds that the old queries could not say: every kernel code, the epilogues, and refusals of both kinds
+    seen = {(a[18], p[0] if isinstance(p, list) else p) for a, p in fplans.items()}
+    assert {(0, _lib.MSG_PLAN_UPCONV), (1, _lib.MSG_PLAN_ROW3), (1, _lib.MSG_PLAN_ROW3N), (1, _lib.MSG_PLAN_PP), (1, _lib.MSG_PLAN_DMA),
+            (1, _lib.MSG_PLAN_REG), (2, _lib.MSG_PLAN_THIN), (3, _lib.MSG_PLAN_ROW3), (3, _lib.MSG_PLAN_PP), (0, _lib.MSG_EINVAL),
+            (0, _lib.MSG_EUNSUPPORTED)} <= seen and (1, _lib.MSG_PLAN_THIN) not in seen
+    assert all(len(p) <= 3 for a, p in fplans.items() if isinstance(p, list) and (a[18] != 3 or p[0] not in (3, 4) or a[9] != a[8]))
+    assert any(len(p) == 5 for p in fplans.values() if isinstance(p, list))
+    assert any(a[14] == 2 for a in fplans) and any(a[15] and a[9] == a[8] // 4 for a in fplans) and any(a[12] == 2 and a[13] == 0 for a in fplans)
+    assert any(a[9] > a[8] >= 128 for a in fplans) and any(a[0] == _lib.MSG_F32_SPLIT and a[9] % 8 == 4 for a in fplans)
     assert len(rows["plan"]) > 2500 and len(rows["wgrad_workspace"]) > 1400
     assert rows["wgrad_plan"][:len(rows["wgrad_workspace"])] == rows["wgrad_workspace"]
     # ... and the grid reaches every branch of the plan (MSG_WPLAN_DMA needs a tuning build's MSG_CONV_VARIANT=1: not covered)
@@ -540,6 +578,79 @@ def test_weight_gradient_codes_before_any_launch():
         # the queries answer the same codes for what they can see
         assert lib.msg_conv2d_wgrad_workspace(*changed(10, 60)) == EINVAL and wgrad_plan(lib, changed(17, 0)) == EINVAL
         assert lib.msg_conv2d_wgrad_workspace(*changed(1, 0)) == 0 and wgrad_plan(lib, changed(1, 0)) == [0] * _lib.MSG_WPLAN_FIELDS
+
+
+def test_forward_codes_before_any_launch():
+    """What msg_conv2d_fprop, msg_conv2d_fprop_act_mask and msg_conv2d_fprop_act_backward answer without reaching a launch, on a
+    geometry of the row-sharing kernel and one of the ping-pong kernel: the codes the commit before fprop_check / fprop_plan_for
+    returned for the same calls (MSG_EINVAL argument checks before MSG_EUNSUPPORTED; alignment only with pointers; the sign-byte
+    and row-sharing gates and the workspace after the plan), and the plan query answers the same codes for what it can see.  The
+    pointers are fake, 16-byte aligned integers: every case returns before one is used.
+    Two kinds of call answer differently since, both wrong in two ways at once: the argument checks now come before the
+    plan everywhere, so (a) a sign-byte mask on a problem of another kernel whose batch is empty or whose arguments are invalid
+    gets the checks' answer (it was MSG_EUNSUPPORTED), and (b) the activation backward, which took its plan without them, answers
+    MSG_EINVAL for an extent <= 0 (it was MSG_EUNSUPPORTED) and MSG_EUNSUPPORTED for a misaligned x / w / y (it launched)."""
+    from multi_stylegan_amd import _lib
+    from multi_stylegan_amd.build import build
+    from tools.gen_dispatch_table import fprop_plan
+    build(verbose=False)
+    lib = _lib.lib()
+    OK, EINVAL, EUNSUPPORTED = _lib.MSG_OK, _lib.MSG_EINVAL, _lib.MSG_EUNSUPPORTED
+    x, w, y, aux, ws = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
+    #       dtype         B   IH   IW   Cx   Ck   OH   OW   N   ldy kh kw s  p  up ps w_batch_stride
+    row3 = [_lib.MSG_BF16, 16, 128, 128, 256, 256, 128, 128, 256, 256, 3, 3, 1, 1, 1, 0, 0]
+    pp = [_lib.MSG_BF16, 16, 128, 128, 256, 256, 128, 128, 256, 256, 1, 1, 1, 0, 1, 0, 0]
+    assert fprop_plan(lib, row3 + [0, 0]) == fprop_plan(lib, row3 + [0, 1]) == [_lib.MSG_PLAN_ROW3, 256, 256]
+    assert fprop_plan(lib, pp + [0, 0]) == fprop_plan(lib, pp + [0, 1]) == fprop_plan(lib, pp + [0, 3]) == [_lib.MSG_PLAN_PP, 256, 256]
+    rows, entries = fprop_plan(lib, row3 + [0, 3])[3:]
+    assert (rows, entries) == (16 * 64 * 2, 16 * 64 * 4)        # 64 pixel tiles per sample: two wave rows, four waves each
+
+    def changed(geom, index, value):
+        return geom[:index] + [value] + geom[index + 1:]
+
+    def fprop(geom, x=x, w=w, y=y):
+        return lib.msg_conv2d_fprop(x, w, None, y, *geom, None)
+
+    def act_mask(geom, x=x, w=w, y=y, mask=None, noise=None):
+        return lib.msg_conv2d_fprop_act_mask(x, w, y, *geom[:14], geom[16], None, noise, None, 1, 0.2, 1.0, mask, None)
+
+    def act_backward(geom, x=x, w=w, y=y, sign_mask=aux, sign_map=None, tile=256, grad_bias=aux, ws=ws, ws_floats=rows * 256):
+        return lib.msg_conv2d_fprop_act_backward(x, w, y, *geom[:14], geom[16], None, 0, sign_mask, tile, tile, sign_map, 256, 0.2, 1.0,
+                                                 grad_bias, None, 1, None, ws, ws_floats, None)
+    for call in (fprop, act_mask, act_backward):
+        assert call(row3, x=None) == EINVAL and call(row3, y=None) == EINVAL
+        assert call(changed(row3, 1, -1)) == EINVAL
+        assert call(changed(row3, 0, 7)) == EUNSUPPORTED                # no such dtype
+        assert call(changed(row3, 5, 224)) == EUNSUPPORTED              # Ck: not whole 128-byte runs
+        assert call(changed(row3, 1, 0)) == OK                          # an empty batch
+        assert call(changed(row3, 1, 0), x=None, w=None, y=None) == OK
+    for call in (fprop, act_mask):
+        assert call(row3, w=w + 8) == EUNSUPPORTED                      # a misaligned pointer
+        assert call(changed(row3, 2, 0)) == EINVAL and call(changed(row3, 9, 0)) == EINVAL
+        assert call(changed(row3, 9, 260)) == EUNSUPPORTED              # ldy: not whole vectors
+    assert fprop(changed(changed(row3, 14, 2), 12, 2)) == EUNSUPPORTED  # zero insertion and a stride
+    assert fprop(changed(changed(row3, 15, 1), 8, 258)) == EUNSUPPORTED  # pixel shuffle of N % 4
+    assert act_mask(row3, noise=aux) == EINVAL                          # noise without its weight
+    assert act_mask(pp, mask=aux) == EUNSUPPORTED                       # sign bytes: the row-sharing kernels alone
+    assert act_mask(changed(pp, 1, 0), mask=aux) == OK and act_mask(pp, mask=aux, x=None) == EINVAL     # (a) above
+    assert act_backward(row3, sign_mask=None) == EINVAL and act_backward(row3, sign_map=aux) == EINVAL   # exactly one sign source
+    assert act_backward(pp) == EUNSUPPORTED                             # no row-sharing kernel: no such epilogue
+    assert act_backward(changed(row3, 12, 2)) == EUNSUPPORTED and act_backward(changed(row3, 13, 0)) == EUNSUPPORTED
+    assert act_backward(changed(row3, 9, 264)) == EUNSUPPORTED          # a pitched output
+    assert act_backward(row3, ws=None) == EINVAL and act_backward(row3, ws_floats=rows * 256 - 1) == EINVAL
+    assert act_backward(row3, tile=96) == EINVAL                        # sign bytes in tiles the kernel cannot read
+    assert act_backward(changed(row3, 2, 0)) == EINVAL and act_backward(row3, y=y + 8) == EUNSUPPORTED   # (b) above
+    # the query: the same codes for what it can see, and at epilogue 3 no partial sums where the launch is MSG_EUNSUPPORTED
+    for epilogue in (0, 1, 2, 3):
+        assert fprop_plan(lib, changed(row3, 1, -1) + [0, epilogue]) == EINVAL
+        assert fprop_plan(lib, changed(row3, 0, 7) + [0, epilogue]) == EUNSUPPORTED
+        assert fprop_plan(lib, changed(row3, 5, 224) + [0, epilogue]) == EUNSUPPORTED
+        assert fprop_plan(lib, changed(row3, 1, 0) + [0, epilogue]) == [0]
+        assert fprop_plan(lib, changed(row3, 9, 260) + [0, epilogue]) == EUNSUPPORTED
+    assert fprop_plan(lib, changed(changed(row3, 14, 2), 12, 2) + [0, 0]) == EUNSUPPORTED
+    assert fprop_plan(lib, changed(changed(row3, 15, 1), 8, 258) + [0, 0]) == EUNSUPPORTED
+    for geom in (pp, changed(row3, 12, 2), changed(row3, 13, 0), changed(row3, 9, 264)):
+        assert len(fprop_plan(lib, geom + [0, 3])) <= 3
 
 
 def test_non_square_conv_geometry_is_refused():

@@ -3,7 +3,7 @@ tests/golden/dispatch_table.json (replayed by tests/test_host.py::test_dispatch_
 
     python -m tools.gen_dispatch_table [--out tests/golden/dispatch_table.json] [--only TABLE]
 
-Host-only: the six queried entries launch nothing, so no GPU is needed.  The grid (the *_rows functions below; a few thousand
+Host-only: the seven queried entries launch nothing, so no GPU is needed.  The grid (the *_rows functions below; a few thousand
 rows): every convolution geometry the two networks issue at 256^2 / batch 16 (+ the discriminator's doubled batch) and 512^2 /
 batch 8 -- forward, data gradient, stride-2 data gradient, sub-pixel up-convolution, the thin RGB / head layers -- with shared and
 per-sample weights at batch 1, 4, 8, 16, 32, 33, and one value on each side of every threshold of the eligibility functions.
@@ -292,10 +292,80 @@ def wgrad_plan(lib, row):
     return list(out) if rc == 0 else rc
 
 
+def fprop_plan_rows():
+    """Arguments of msg_conv2d_fprop_launch_plan: dtype .. w_batch_stride as msg_conv2d_fprop takes them, has_bias, epilogue (0 plain,
+    1 fused activation, 2 residual merge, 3 activation backward)."""
+    # plan_rows() with what msg_conv2d_fprop_plan assumes spelled out: ldy = N rounded up to 8, stride 1, 'same' padding, no bias
+    rows = [r[:9] + [max(8, (r[8] + 7) // 8 * 8)] + r[9:11] + [1, r[9] // 2, 1, 0, r[11], 0, 0] for r in plan_rows()]
+
+    def add(dtype, b, ih, iw, cx, ck, oh, ow, n, kh, kw, stride, pad, per_sample, in_up=1, shuffle=0, ldy=None, bias=0, epilogue=0,
+            wstride=None):
+        ldy = (max(8, (n + 7) // 8 * 8) if not shuffle else n // 4) if ldy is None else ldy
+        wstride = (n * (1 if shuffle else kh * kw) * ck if wstride is None else wstride) if per_sample else 0
+        rows.append([dtype, b, ih, iw, cx, ck, oh, ow, n, ldy, kh, kw, stride, pad, in_up, shuffle, wstride, bias, epilogue])
+
+    # the models' launches at batch 16, as conv_ops issues them: every epilogue, and the plain form with a bias
+    for ps in (0, 1):
+        for bias, epilogue in ((1, 0), (0, 1), (0, 2), (0, 3)):
+            for cin, cout, sizes in LAYERS:
+                for r in sizes:
+                    for k in (1, 3):
+                        add(BF16, 16, r, r, cin, cin, r, r, cout, k, k, 1, k // 2, ps, bias=bias, epilogue=epilogue)
+            for r in SIZES:                                                                     # the thin layers
+                add(BF16, 16, r, r, 512, 512, r, r, 6, 1, 1, 1, 0, ps, bias=bias, epilogue=epilogue)
+                add(BF16, 16, r, r, 8, 64, r, r, 512, 1, 1, 1, 0, ps, bias=bias, epilogue=epilogue)
+                add(BF16, 16, r, r, 8, 64, r, r, 128, 1, 1, 1, 0, ps, bias=bias, epilogue=epilogue)
+                add(BF16, 16, r, r, 128, 128, r, r, 1, 1, 1, 1, 0, ps, bias=bias, epilogue=epilogue)
+            for c, sizes in STRIDE2:                                                            # real stride 2, no padding
+                for r in sizes:
+                    add(BF16, 16, r, r, c, c, r // 2 - 1, r // 2 - 1, c, 3, 3, 2, 0, ps, bias=bias, epilogue=epilogue)
+        for bias in (0, 1):                                 # what the old queries could not say: pixel shuffle (ldy = N / 4), in_up
+            for c, sizes in STRIDE2:                        # the stride-2 data gradient, sub-pixel form: 2x2 taps, padding 1
+                for r in sizes:
+                    add(BF16, 16, r // 2 - 1, r // 2 - 1, c, c, r // 2, r // 2, 4 * c, 2, 2, 1, 1, ps, shuffle=1, bias=bias)
+            for r in SIZES:
+                for b in (1, 2, 16):                        # the sub-pixel up-convolution (its own kernel from 128^2 maps on) ...
+                    add(BF16, b, r, r, 512, 512, r, r, 2048, 1, 1, 1, 0, ps, shuffle=1, bias=bias)
+                if r >= 8:                                  # ... and its data gradient
+                    add(BF16, 16, r, r, 512, 512, r // 2, r // 2, 512, 2, 2, 2, 0, ps, bias=bias)
+                add(BF16, 16, r, r, 512, 512, 2 * r, 2 * r, 512, 3, 3, 1, 1, ps, in_up=2, bias=bias)   # zero insertion (transposed 3x3)
+        add(BF16, 16, 128, 128, 512, 512, 128, 128, 2048, 1, 1, 1, 0, ps, shuffle=1, wstride=512)      # weight sets that overlap
+    for epilogue in (0, 1, 2, 3):
+        for n, ldy in ((256, 384), (128, 384), (512, 520)):                                  # a channel slice of a wider map
+            for k in (1, 3):
+                add(BF16, 16, 128, 128, 256, 256, 128, 128, n, k, k, 1, k // 2, 0, ldy=ldy, epilogue=epilogue)
+        add(BF16, 16, 256, 256, 8, 64, 256, 256, 128, 1, 1, 1, 0, 0, ldy=136, epilogue=epilogue)
+    for dtype in (F32, SPLIT):                                                                # fp32: ldy a multiple of 4
+        for n in (6, 12, 100, 128):
+            for k, cx in ((1, 128), (3, 128), (1, 256), (3, 100)):
+                for epilogue in (0, 1, 2):
+                    add(dtype, 16, 64, 64, cx, (cx + 31) // 32 * 32, 64, 64, n, k, k, 1, k // 2, 0, ldy=(n + 3) // 4 * 4, epilogue=epilogue)
+    base = dict(dtype=BF16, b=16, ih=128, iw=128, cx=256, ck=256, oh=128, ow=128, n=256, kh=3, kw=3, stride=1, pad=1, per_sample=0)
+    refused = (dict(b=0), dict(b=-1), dict(ih=0), dict(n=0), dict(kh=0), dict(stride=0), dict(in_up=0), dict(ck=0), dict(ldy=0),   # MSG_EINVAL,
+               dict(epilogue=4), dict(epilogue=-1), dict(epilogue=1, bias=1), dict(epilogue=2, in_up=2), dict(epilogue=3, shuffle=1),
+               dict(dtype=2), dict(dtype=7), dict(ck=224), dict(cx=260, ck=320), dict(ldy=260), dict(n=258, shuffle=1),        # MSG_EUNSUPPORTED
+               dict(n=240, shuffle=1, ldy=64), dict(in_up=2, stride=2), dict(dtype=F32, ck=272), dict(dtype=SPLIT, cx=258),
+               dict(ck=32704, cx=32704, kh=1, kw=1, pad=0, n=128), dict(ck=32640, cx=32640, kh=1, kw=1, pad=0, n=128))           # K sweep against the 64 KiB zero page: 511 / 510 steps
+    for change in refused:
+        add(**{**base, **change})
+    return rows
+
+
+def fprop_plan(lib, row):
+    """msg_conv2d_fprop_launch_plan's answer for a row: the MSG_FPLAN_FIELDS fields without trailing zeros, or its negative code."""
+    import ctypes
+    out = (ctypes.c_longlong * 5)()
+    rc = lib.msg_conv2d_fprop_launch_plan(*row, ctypes.addressof(out), 5)
+    fields = list(out)
+    while len(fields) > 1 and not fields[-1]:
+        fields.pop()
+    return fields if rc == 0 else rc
+
+
 ROWS = {"plan": plan_rows, "upconv_eligible": upconv_rows, "thin_eligible": thin_rows, "wgrad_workspace": wgrad_rows}
 # every table of the file: the four above as they always were (a reader that knows only them still finds each of its digests), and
-# the weight-gradient plans
-ALL_ROWS = {**ROWS, "wgrad_plan": wgrad_plan_rows}
+# the weight-gradient plans and the plans of the forward family
+ALL_ROWS = {**ROWS, "wgrad_plan": wgrad_plan_rows, "fprop_plan": fprop_plan_rows}
 
 
 def digest(rows):
@@ -315,6 +385,7 @@ def evaluate(lib):
     out["thin_eligible"] = [lib.msg_conv2d_fprop_thin_eligible(*r) for r in thin_rows()]
     out["wgrad_workspace"] = [lib.msg_conv2d_wgrad_workspace(*r) for r in wgrad_rows()]
     out["wgrad_plan"] = [wgrad_plan(lib, r) for r in wgrad_plan_rows()]
+    out["fprop_plan"] = [fprop_plan(lib, r) for r in fprop_plan_rows()]
     return out
 
 
