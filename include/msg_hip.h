@@ -684,6 +684,40 @@ int msg_gan_loss_backward(const void* pred_real, const void* pred_fake, const fl
                           void* grad_real, void* grad_fake, int dtype, int kind, int aux_mode,
                           long long n_real, long long n_fake, long long P, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Elastic deformation of a batch of frames: the dataset's augmentation for a whole batch in one call.  Replaces the dense
+ * (4 sigma + 1)^2 conv2d of two noise planes and the grid_sample call per sample of dataset/tlfm_dataset.py:230-275
+ * (elastic_deformation, which ElasticDeformation.forward at :221-227 calls).
+ * in     [B, F, H, W] MSG_F32 or MSG_BF16 (read as stored, all arithmetic fp32), contiguous
+ * noise  [B, 2, H, W] fp32 in [-1, 1): plane 0 the horizontal component (the reference's FIRST torch.rand draw), plane 1 the
+ *        vertical one
+ * field  [B, 2, H, W] fp32, every element written: the displacement in pixels,
+ *          d[c, y, x] = alpha sum_i sum_j g[i] g[j] noise[c, y + i - 2 sigma, x + j - 2 sigma],
+ *          g[i] = exp(-(i - 2 sigma)^2 / (2 sigma^2)) / (sqrt(2 pi) sigma), i = 0 .. 4 sigma
+ *        -- the reference's kernel, which is exactly g (x) g: truncated at +-2 sigma and NOT renormalised (sum g ~ 0.954); noise
+ *        outside the frame counts as zero.  Evaluated separably (row pass, column pass) with fp32 multiply-adds.  One field per
+ *        sample, shared by its F frames.
+ * out    [B, F, H, W] in the dtype of `in`, every element written, not aliasing `in`: the bilinear sample of each frame at
+ *          px = ((gx + 1) W - 1) / 2,  gx = 2 (x + d[0, y, x] - H / 2) / H   (integer H / 2)
+ *          py = ((gy + 1) H - 1) / 2,  gy = 2 (y + d[1, y, x] - W / 2) / W
+ *        -- the x coordinate is divided by the HEIGHT and the y coordinate by the width, as the reference does (:269-270);
+ *        grid_sample's align_corners=False un-normalisation; px clamped to [0, W - 1], py to [0, H - 1] (border padding);
+ *        neighbours floor and floor + 1, the upper index clamped to the frame.  The four indices and weights of a position are
+ *        computed once and applied to all F frames.  bf16: rounded to nearest even on the store.
+ * ws     msg_elastic_workspace(B, H, W) BYTES (the row pass's output, one more [B, 2, H, W] fp32 array), 16-byte aligned; needs
+ *        no initialisation and carries nothing between calls.  Two launches, no synchronisation.
+ * Deterministic: no atomics, nothing depends on workgroup order, a sample's result does not depend on the rest of the batch.
+ * W a multiple of 4 (fp32) / 8 (bf16) and 16-byte aligned in / out / field: 16-byte stores; anything else a scalar path with the
+ * same arithmetic and the same bits.
+ * MSG_EINVAL: a NULL pointer (ws included), a non-positive size, sigma < 1, H W or the row pass's block count above 2^31 - 1.
+ * MSG_EUNSUPPORTED: any other dtype; sigma > MSG_ELASTIC_MAX_SIGMA (the halo the LDS tiles are sized for).  Nothing is launched
+ * in any of these cases.
+ * ------------------------------------------------------------------------- */
+#define MSG_ELASTIC_MAX_SIGMA 32
+long long msg_elastic_workspace(int B, int H, int W);
+int msg_elastic_deform(const void* in, const float* noise, float* field, void* out, int dtype,
+                       int B, int F, int H, int W, int sigma, float alpha, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

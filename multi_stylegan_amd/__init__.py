@@ -4,6 +4,7 @@ from .adaptive_discriminator_augmentation import AdaptiveDiscriminatorAugmentati
 from .config import (generation_hyperparameters, multi_style_gan_generator_config,
                      u_net_2d_discriminator_config)
 from .data import DevicePrefetcher, SyntheticBatches, TLFMDeviceFeed, prepare_tlfm_batch
+from .elastic import ElasticDeformation, elastic_deform_batch, elastic_deformation
 from .inference import GeneratorSampler, load_generator_ema, split_sequences, validation_samples
 from .loss import (HingeDiscriminatorLoss, HingeDiscriminatorLossCutMix, HingeGeneratorLoss, PathLengthRegularization,
                    R2Regularization, TopK, WassersteinDiscriminatorLoss, WassersteinDiscriminatorLossCutMix,
@@ -22,4 +23,5 @@ __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper
            "sample_sheets", "write_png", "SheetWriter", "save_prediction", "epoch_sample_dump", "dump_samples", "interpolation_latents",
            "interpolation_frames", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters",
            "WassersteinDiscriminatorLoss", "WassersteinDiscriminatorLossCutMix", "WassersteinGeneratorLoss", "HingeGeneratorLoss",
-           "HingeDiscriminatorLoss", "HingeDiscriminatorLossCutMix", "R2Regularization"]
+           "HingeDiscriminatorLoss", "HingeDiscriminatorLossCutMix", "R2Regularization", "ElasticDeformation", "elastic_deformation",
+           "elastic_deform_batch"]

@@ -14,7 +14,8 @@ whenever the batch is pageable.  Here:
   dataset/tlfm_dataset.py:187,191): what the benchmark and smoke runs use when there is no dataset.
 * ``prepare_tlfm_batch`` / ``TLFMDeviceFeed`` feed the real dataset (``tlfm_dataset.TFLMDatasetGAN(..., raw=True)``): the
   camera's 16-bit counts cross the bus as they are (half the bytes of the reference's fp32 frames) and one streaming kernel
-  call per batch (csrc/tlfm_prepare.hip) does the normalisation and the flips the reference does per sample on the host.
+  call per batch (csrc/tlfm_prepare.hip) does the normalisation and the flips the reference does per sample on the host;
+  ``TLFMDeviceFeed(..., elastic=...)`` adds the dataset's elastic deformation (elastic.py, csrc/elastic.hip) behind it.
 
 ``ModelWrapper.train`` / ``_gan_training`` put every host iterable behind a ``DevicePrefetcher`` themselves.
 """
@@ -25,6 +26,7 @@ from typing import Any, Iterable, Iterator, Optional, Union
 import torch
 
 from . import _lib
+from .elastic import ElasticDeformation
 
 
 def _map(fn, batch):
@@ -292,10 +294,25 @@ class TLFMDeviceFeed:
     ``TFLMDatasetGAN(..., raw=True)`` (default-collated: uint16 ``[B, C, T, H, W]``, uint8 ``[B]``); they cross the bus as
     counts through a ``DevicePrefetcher`` and each is normalised on the compute stream by ``prepare_tlfm_batch``
     (``prepare_kwargs``: its keyword arguments).  A yielded batch is a fresh tensor: it stays valid for as long as the consumer
-    keeps it, and the prefetcher's slot behind it is reused as soon as the consumer asks for the next batch."""
+    keeps it, and the prefetcher's slot behind it is reused as soon as the consumer asks for the next batch.
 
-    def __init__(self, loader: Iterable, device: Union[str, torch.device] = "cuda", depth: int = 2, **prepare_kwargs):
+    ``elastic``: an ``elastic.ElasticDeformation`` -- every batch is deformed on the compute stream right after the prepare
+    (``elastic_deform_batch``: one field per sample, noise from the module's generator), in the dtype the prepare wrote.  None:
+    no deformation, the prepared batch itself.  The feed deforms the NORMALISED, FLIPPED frames, whereas the reference's
+    ``Compose`` (and this module used as ``TFLMDatasetGAN(..., raw=False, transformations=...)``, which keeps the reference's
+    order exactly) deforms the counts BEFORE normalisation: here the bright-field minimum and maximum are taken before the
+    interpolation instead of after it (an interpolated frame's extremes lie inside the original's, so the reference's output
+    always spans [0, 1] and this one may not), and GFP / RFP are clamped before they are interpolated instead of after."""
+
+    def __init__(self, loader: Iterable, device: Union[str, torch.device] = "cuda", depth: int = 2,
+                 elastic: Optional[ElasticDeformation] = None, **prepare_kwargs):
+        if elastic is not None:
+            if not isinstance(elastic, ElasticDeformation):
+                raise ValueError(f"elastic is an ElasticDeformation or None, got {type(elastic).__name__}")
+            if elastic.sample_mode != "bilinear":
+                raise ValueError(f"sample_mode {elastic.sample_mode!r}: the device path samples bilinearly only")
         self.feed = DevicePrefetcher(loader, device, depth)
+        self.elastic = elastic
         self.prepare_kwargs = prepare_kwargs
 
     def __len__(self) -> int:
@@ -303,7 +320,8 @@ class TLFMDeviceFeed:
 
     def __iter__(self) -> Iterator[torch.Tensor]:
         for frames, hflip in self.feed:
-            yield prepare_tlfm_batch(frames, hflip, **self.prepare_kwargs)
+            batch = prepare_tlfm_batch(frames, hflip, **self.prepare_kwargs)
+            yield batch if self.elastic is None else self.elastic.deform_batch(batch)
 
 
 def prefetch(loader: Iterable, device: Union[str, torch.device], depth: int = 2,

@@ -6,6 +6,8 @@ builds), without its cv2 / torchvision dependencies, and with a second mode that
   ``raw=False`` returns the reference's normalised float32 ``[C, T, H, W]``; ``raw=True`` returns the untouched 16-bit counts
   and the horizontal-flip decision, for ``data.TLFMDeviceFeed`` / ``data.prepare_tlfm_batch`` to normalise on the device:
   half the bytes over the bus and no float arithmetic on the host.
+* ``ElasticDeformation`` / ``elastic_deformation`` (dataset/tlfm_dataset.py:201-275) live in ``elastic.py`` and are importable from
+  here, as in the reference.
 """
 import os
 import struct
@@ -16,6 +18,7 @@ import torch
 from torch.utils.data import Dataset
 
 from .data import prepare_tlfm_batch
+from .elastic import ElasticDeformation, elastic_deformation          # (where the reference defines them)
 
 _TYPE_CODES = {1: "B", 3: "H", 4: "I", 6: "b", 8: "h", 9: "i"}          # the integer field types (BYTE, SHORT, LONG and signed)
 _TAG_NAMES = {258: "BitsPerSample", 259: "Compression", 262: "PhotometricInterpretation", 274: "Orientation",
