@@ -461,10 +461,21 @@ def test_few_row_linear_family(m, n, k):
     assert gwe.abs().max().item() == 0.0
 
 
-@pytest.mark.parametrize("batch", [3, 21])          # 21: more than the 16 samples one backward launch takes (chunked)
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("kind", ["conv3x3_demod", "up2x2_demod", "torgb1x1_nodemod"])
-def test_fused_modulated_conv_matches_composite(kind, dtype, batch):
+# kind x storage x batch (21: more than the 16 samples one backward launch takes: chunked) on 40 -> 24 channels (3 for the 1x1), 10x10;
+# then, with (I, O, map side) of their own: 512 output channels at batch 5 -- msg_modulate_weights takes four samples per
+# workgroup and a ragged last group of one (what training meets at 512 channels), the fold two output channels per workgroup --
+# and 6 input channels in fp32 storage, which the fold's generic kernel takes (I % 4 != 0)
+FUSED_MOD_CASES = [pytest.param(kind, dt, batch, None, id=f"{kind}-dtype{j}-{batch}")
+                   for kind in ("conv3x3_demod", "up2x2_demod", "torgb1x1_nodemod")
+                   for j, dt in enumerate((torch.float32, torch.bfloat16)) for batch in (3, 21)] + [
+    pytest.param("conv3x3_demod", torch.float32, 5, (8, 512, 4), id="conv3x3_demod-dtype0-5-O512-ragged-sample-group"),
+    pytest.param("conv3x3_demod", torch.bfloat16, 5, (8, 512, 4), id="conv3x3_demod-dtype1-5-O512-ragged-sample-group"),
+    pytest.param("conv3x3_demod", torch.float32, 3, (6, 24, 10), id="conv3x3_demod-dtype0-3-I6-generic-fold"),
+]
+
+
+@pytest.mark.parametrize("kind,dtype,batch,shape", FUSED_MOD_CASES)
+def test_fused_modulated_conv_matches_composite(kind, dtype, batch, shape):
     """csrc/modulate.hip path (demod reduction, per-sample weights in kernel layout, fused backward) against the
     composite torch-op formulation AND against the CPU oracle, forward and all three gradients."""
     from multi_stylegan_amd import conv_ops
@@ -472,7 +483,7 @@ def test_fused_modulated_conv_matches_composite(kind, dtype, batch):
     tol = TOLS[dtype] * (3 if dtype == torch.float32 else 1)
     k = {"conv3x3_demod": 3, "up2x2_demod": 2, "torgb1x1_nodemod": 1}[kind]
     demod, up = kind != "torgb1x1_nodemod", kind == "up2x2_demod"
-    b, i, o, h = batch, 40, (3 if k == 1 else 24), 10
+    b, (i, o, h) = batch, shape or (40, (3 if k == 1 else 24), 10)
     g = torch.Generator().manual_seed(k)
     x = torch.randn(b, i, h, h, generator=g).to(dtype).float()
     w = torch.randn(1, o, i, k, k, generator=g)
@@ -499,7 +510,7 @@ def test_fused_modulated_conv_matches_composite(kind, dtype, batch):
         gd = torch.autograd.grad(y, (xd, wd, sd), gyd)
     finally:
         conv_ops._modconv_backward = orig
-    assert calls == ([3] if batch == 3 else [16, 5]), "the fused backward must run, in chunks of at most 16 samples"
+    assert calls == {3: [3], 5: [5], 21: [16, 5]}[batch], "the fused backward must run, in chunks of at most 16 samples"
     yc = conv_ops._modulated_composite(xd, wd, sd, demod, up)
     gc = torch.autograd.grad(yc, (xd, wd, sd), gyd)
     assert rel_err(y.float(), yr) < tol and rel_err(y.float(), yc.float()) < tol
