@@ -618,6 +618,35 @@ int msg_tlfm_prepare(const unsigned short* raw, const unsigned char* hflip, void
                      unsigned int* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * The resident dataset: every frame decoded once into one store of counts in device memory, a batch built by one launch that
+ * gathers, normalises and flips the frames its samples name.  Replaces the per-epoch re-read of every file in the DataLoader
+ * workers -- dataset/tlfm_dataset.py:128-198 (__getitem__: cv2.imread of every frame of every sample, the normalisation, the
+ * flips), dataset/utils.py:4-23 (normalize_0_1) and the DataLoader of train_multi_stylegan.py:60-63 with its collate, pinned
+ * staging and host-to-device copy.
+ * frames [N, H, W] unsigned 16-bit counts, contiguous: the store
+ * range  [N, 2] 32-bit words: the integer (min, max) of each frame.  msg_tlfm_frame_range writes it -- one launch, one
+ *        workgroup per frame, integer min / max without atomics: deterministic, equal to numpy's.  Once per store.
+ * index  [B, C, T] int32 frame ids in device memory: out[b, c, t] is made from frames[index[b, c, t]]
+ * hflip, out, dtype, vflip, lo1 .. div2: as msg_tlfm_prepare
+ * channel 0: lo = (float) min, div = (float) max - lo from range[id]; channels 1 / 2: (lo1, div1) / (lo2, div2).  The same
+ *            arithmetic as msg_tlfm_prepare (IEEE subtract and divide, the clamps in the reference's order, flips on the store
+ *            side): the MSG_F32 result equals msg_tlfm_prepare's on the stacked frames bit for bit, MSG_BF16 is its
+ *            round-to-nearest-even; a constant bright-field frame is NaN in every pixel.
+ * One launch, no workspace, no atomics, nothing carried between calls.  A frame is split over workgroups in row ranges of
+ * ~4096 pixels; W % 8 == 0 and 16-byte aligned store and output bases: 16-byte loads, anything else the scalar path.  A
+ * frame's offset in the store is 64-bit (N * H * W may exceed 2^31 elements).
+ * An id outside [0, N) never reads the store: the check is uniform per workgroup and that frame of `out` is NaN throughout.
+ * MSG_EINVAL (both): a non-positive size, C > 3, any other dtype, NULL frames / range / index / out, more frames (or frames
+ * and splits) than the launch's block index can address.
+ * ------------------------------------------------------------------------- */
+int msg_tlfm_frame_range(const unsigned short* frames, long long N, int H, int W,
+                         unsigned int* range, void* stream);
+int msg_tlfm_gather(const unsigned short* frames, const unsigned int* range, long long N,
+                    const int* index, const unsigned char* hflip, void* out, int dtype,
+                    int B, int C, int T, int H, int W, int vflip,
+                    float lo1, float div1, float lo2, float div2, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Sample output: a generated batch -> the 8-bit RGB pictures the reference writes through torchvision.utils.save_image, composed
  * in one pass.  Replaces the repeat_interleave / zero-fill / cat / permute chains, the fp32 device-to-host copy and the host
  * quantisation of multi_stylegan/misc.py:132-166 (Logger.save_prediction, called at model_wrapper.py:166-174),

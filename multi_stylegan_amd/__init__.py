@@ -11,6 +11,7 @@ from .loss import (HingeDiscriminatorLoss, HingeDiscriminatorLossCutMix, HingeGe
                    WassersteinGeneratorLoss)
 from .model_wrapper import Draws, ModelWrapper
 from .multi_stylegan_generator import Generator as MultiStyleGANGenerator
+from .resident import ResidentTLFMFeed, ResidentTLFMStore, gather_tlfm_batch
 from .u_net_2d_discriminator import Discriminator as MultiStyleGANDiscriminator
 from .samples import (SheetWriter, dump_samples, epoch_sample_dump, interpolation_frames, interpolation_latents, sample_sheets,
                       save_prediction, write_png)
@@ -24,4 +25,4 @@ __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper
            "interpolation_frames", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters",
            "WassersteinDiscriminatorLoss", "WassersteinDiscriminatorLossCutMix", "WassersteinGeneratorLoss", "HingeGeneratorLoss",
            "HingeDiscriminatorLoss", "HingeDiscriminatorLossCutMix", "R2Regularization", "ElasticDeformation", "elastic_deformation",
-           "elastic_deform_batch"]
+           "elastic_deform_batch", "ResidentTLFMStore", "ResidentTLFMFeed", "gather_tlfm_batch"]

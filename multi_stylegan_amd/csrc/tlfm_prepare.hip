@@ -196,3 +196,118 @@ extern "C" int msg_tlfm_prepare(const unsigned short* raw, const unsigned char* 
         tlfm_launch<float>(raw, hflip, (float*)out, B, C, T, H, W, vflip, lo1, div1, lo2, div2, ws, s);
     return MSG_CHECK_LAUNCH();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The resident dataset (resident.py): every frame of the dataset decoded once into one store [N, H, W] of counts in HBM, a
+// batch built by ONE launch that gathers the frames its samples name.  Replaces the per-epoch re-read of
+// dataset/tlfm_dataset.py:128-198 in the DataLoader workers of train_multi_stylegan.py:60-63 and, with it, the first of the
+// two launches above: a frame's bright-field minimum and maximum do not change between epochs, so they are computed when the
+// store is built (tlfm_frame_range_kernel) and the gather reads one (min, max) pair per frame instead of a workspace.
+// The arithmetic is tlfm_value / tlfm_rows above, unchanged -- the fp32 result equals msg_tlfm_prepare's on the stacked frames.
+
+// one workgroup per frame: range[2 f] = min, range[2 f + 1] = max of its P counts (integers: order-independent, deterministic)
+template <bool VEC>
+__global__ __launch_bounds__(256) void tlfm_frame_range_kernel(const unsigned short* __restrict__ frames,
+                                                               unsigned int* __restrict__ range, long long P) {
+    const long long f = blockIdx.x;
+    const unsigned short* src = frames + f * P;
+    const long long items = VEC ? P / 8 : P;
+    unsigned int lo = 0xffffffffu, hi = 0u;
+    for (long long i = threadIdx.x; i < items; i += 256) {
+        if constexpr (VEC) {
+            unsigned int px[8];
+            tlfm_unpack8(*reinterpret_cast<const uint4*>(src + i * 8), px);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { lo = min(lo, px[e]); hi = max(hi, px[e]); }
+        } else {
+            const unsigned int x = src[i];
+            lo = min(lo, x); hi = max(hi, x);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = min(lo, (unsigned int)__shfl_xor((int)lo, off, 64));
+        hi = max(hi, (unsigned int)__shfl_xor((int)hi, off, 64));
+    }
+    __shared__ unsigned int s_lo[4], s_hi[4];
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        range[2 * f] = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
+        range[2 * f + 1] = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
+    }
+}
+
+// block (f, s) of B*C*T x S, flat; f is also the position in `index` [B, C, T].  The frame id is one uniform load, the bounds
+// check on it uniform per workgroup: an id outside [0, N) reads nothing and fills its share of the output frame with NaN.
+template <typename OT, bool VEC>
+__global__ __launch_bounds__(256) void tlfm_gather_kernel(const unsigned short* __restrict__ frames,
+                                                          const unsigned int* __restrict__ range, long long N,
+                                                          const int* __restrict__ index, const unsigned char* __restrict__ hflip,
+                                                          OT* __restrict__ out, int C, int T, int H, int W, int S, int vflip,
+                                                          float lo1, float div1, float lo2, float div2) {
+    const long long f = blockIdx.x / S;
+    const int s = (int)(blockIdx.x - f * S);
+    const long long b = f / ((long long)C * T);
+    const int c = (int)((f / T) % C);
+    const long long P = (long long)H * W;
+    const int per = (H + S - 1) / S;
+    const int r0 = s * per < H ? s * per : H, r1 = r0 + per < H ? r0 + per : H;
+    OT* dst = out + f * P;
+    const long long id = index[f];
+    if (id < 0 || id >= N) {
+        const float nan = __builtin_nanf("");
+        for (long long i = (long long)r0 * W + threadIdx.x; i < (long long)r1 * W; i += 256) store_from_f32<OT>(dst + i, nan);
+        return;
+    }
+    const unsigned short* src = frames + id * P;                                  // 64-bit: N * P may exceed 2^31 elements
+    const bool hf = hflip != nullptr && hflip[b] != 0;
+    if (c == 0) {
+        const float lo = (float)range[2 * id];
+        tlfm_rows<OT, VEC, false>(src, dst, H, W, r0, r1, hf, vflip, lo, (float)range[2 * id + 1] - lo);
+    } else {
+        tlfm_rows<OT, VEC, true>(src, dst, H, W, r0, r1, hf, vflip, c == 1 ? lo1 : lo2, c == 1 ? div1 : div2);
+    }
+}
+
+extern "C" int msg_tlfm_frame_range(const unsigned short* frames, long long N, int H, int W, unsigned int* range, void* stream) {
+    if (N <= 0 || H <= 0 || W <= 0 || !frames || !range) return MSG_EINVAL;
+    if (N > 0x7fffffffll) return MSG_EINVAL;                                      // (one block index per frame)
+    const long long P = (long long)H * W;
+    hipStream_t s = (hipStream_t)stream;
+    if (P % 8 == 0 && (((uintptr_t)frames) & 15u) == 0)
+        hipLaunchKernelGGL((tlfm_frame_range_kernel<true>), dim3((unsigned)N), dim3(256), 0, s, frames, range, P);
+    else
+        hipLaunchKernelGGL((tlfm_frame_range_kernel<false>), dim3((unsigned)N), dim3(256), 0, s, frames, range, P);
+    return MSG_CHECK_LAUNCH();
+}
+
+template <typename OT>
+static void tlfm_gather_launch(const unsigned short* frames, const unsigned int* range, long long N, const int* index,
+                               const unsigned char* hflip, OT* out, int B, int C, int T, int H, int W, int vflip, float lo1,
+                               float div1, float lo2, float div2, hipStream_t s) {
+    const int S = tlfm_split(H, W);
+    const bool vec = W % 8 == 0 && ((((uintptr_t)frames) | ((uintptr_t)out)) & 15u) == 0;
+    const unsigned blocks = (unsigned)((long long)B * C * T * S);
+    if (vec)
+        hipLaunchKernelGGL((tlfm_gather_kernel<OT, true>), dim3(blocks), dim3(256), 0, s, frames, range, N, index, hflip, out, C,
+                           T, H, W, S, vflip, lo1, div1, lo2, div2);
+    else
+        hipLaunchKernelGGL((tlfm_gather_kernel<OT, false>), dim3(blocks), dim3(256), 0, s, frames, range, N, index, hflip, out, C,
+                           T, H, W, S, vflip, lo1, div1, lo2, div2);
+}
+
+extern "C" int msg_tlfm_gather(const unsigned short* frames, const unsigned int* range, long long N, const int* index,
+                               const unsigned char* hflip, void* out, int dtype, int B, int C, int T, int H, int W, int vflip,
+                               float lo1, float div1, float lo2, float div2, void* stream) {
+    if (N <= 0 || B <= 0 || C <= 0 || C > 3 || T <= 0 || H <= 0 || W <= 0 || !frames || !range || !index || !out)
+        return MSG_EINVAL;
+    if (dtype != MSG_F32 && dtype != MSG_BF16) return MSG_EINVAL;
+    if ((long long)B * C * T * TLFM_MAX_SPLIT > 0x7fffffffll) return MSG_EINVAL;      // (one block index per frame and split)
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == MSG_BF16)
+        tlfm_gather_launch<bf16_t>(frames, range, N, index, hflip, (bf16_t*)out, B, C, T, H, W, vflip, lo1, div1, lo2, div2, s);
+    else
+        tlfm_gather_launch<float>(frames, range, N, index, hflip, (float*)out, B, C, T, H, W, vflip, lo1, div1, lo2, div2, s);
+    return MSG_CHECK_LAUNCH();
+}

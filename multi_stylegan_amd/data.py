@@ -16,6 +16,8 @@ whenever the batch is pageable.  Here:
   camera's 16-bit counts cross the bus as they are (half the bytes of the reference's fp32 frames) and one streaming kernel
   call per batch (csrc/tlfm_prepare.hip) does the normalisation and the flips the reference does per sample on the host;
   ``TLFMDeviceFeed(..., elastic=...)`` adds the dataset's elastic deformation (elastic.py, csrc/elastic.hip) behind it.
+* ``resident.ResidentTLFMStore`` / ``resident.ResidentTLFMFeed`` keep the whole dataset's counts in device memory instead and
+  build each batch with one gather launch: nothing of this module runs per step.
 
 ``ModelWrapper.train`` / ``_gan_training`` put every host iterable behind a ``DevicePrefetcher`` themselves.
 """
@@ -328,7 +330,8 @@ def prefetch(loader: Iterable, device: Union[str, torch.device], depth: int = 2,
              transfer_dtype: Optional[torch.dtype] = None) -> Iterable:
     """``loader`` behind a DevicePrefetcher when that helps (a GPU target and a loader that is not already one of this
     module's device-side feeds); otherwise the loader itself."""
+    from .resident import ResidentTLFMFeed                                 # (imports this module)
     device = torch.device(device)
-    if device.type != "cuda" or isinstance(loader, (DevicePrefetcher, SyntheticBatches, TLFMDeviceFeed)):
+    if device.type != "cuda" or isinstance(loader, (DevicePrefetcher, SyntheticBatches, TLFMDeviceFeed, ResidentTLFMFeed)):
         return loader
     return DevicePrefetcher(loader, device, depth, transfer_dtype)
