@@ -203,9 +203,18 @@ int msg_bias_act_backward_mask_head(const void* gy, const void* ghead, const flo
  *   Data gradients are the same entry with the caller's re-laid weights.
  * msg_conv2d_wgrad:
  *   gw[(b)][o][tap][i] (+)= sum_{pixels} gy[b,oh,ow,o] * x[b, oh*stride+kh-pad, ow*stride+kw-pad, i]
- *   gw fp32 [(B)][O][kh*kw][ldgw] (ldgw % 4 == 0), OVERWRITTEN; per_sample = 1: one result per sample (its pixels split
- *   into k_chunks K-slices), otherwise ONE result for the whole batch (the library folds the batch into K and chooses the
- *   number of K-slices itself; k_chunks is ignored unless folding is impossible).
+ *   gw fp32 [(B)][O][kh*kw][ldgw] (ldgw % 4 == 0), OVERWRITTEN; per_sample = 1: one result per sample, otherwise ONE result
+ *   for the whole batch.  k_chunks (the same in msg_conv2d_wgrad_workspace and msg_conv2d_wgrad_plan):
+ *     MSG_WGRAD_K_AUTO  the library's own split for this problem -- what callers pass unless they have a reason not to.  It is
+ *                       resolved to a positive number first (for per-sample weights one K sweep per sample, or a few K-slices
+ *                       where that leaves most of the chip idle; for shared weights at most 65535 / B), and the call then
+ *                       goes on exactly as if the caller had passed that number.  Shared weights with more than 65535 samples
+ *                       resolve to 0 slices: MSG_EINVAL, as k_chunks = 0 is.
+ *     k_chunks >= 1     per_sample = 1: the pixels of a sample are split into k_chunks K-slices (on the kh x 3 row-sharing
+ *                       kernel 1 means "no opinion": that kernel's own model chooses).  per_sample = 0: the library folds the batch into K and chooses
+ *                       the number of K-slices itself; k_chunks slices per sample only where folding is impossible (2^31 pixels
+ *                       or more in the batch).
+ *     0, or any other negative value: MSG_EINVAL.
  *   A result that is the sum of several K-slices is formed deterministically: every slice stores its partial result into
  *   its own slab of `ws` (float32, at least msg_conv2d_wgrad_workspace(...) elements -- 0 when nothing is split; contents
  *   irrelevant) and a second launch adds the slabs in slice order.  No float atomics: identical inputs give bit-identical
@@ -217,6 +226,7 @@ int msg_conv2d_fprop(const void* x, const void* w, const float* bias, void* y, i
                      int B, int IH, int IW, int Cx, int Ck, int OH, int OW, int N, int ldy,
                      int kh, int kw, int stride, int pad, int in_up, int pixel_shuffle,
                      long long w_batch_stride, void* stream);
+enum { MSG_WGRAD_K_AUTO = -1 };
 int msg_conv2d_wgrad(const void* gy, const void* x, float* gw, int dtype,
                      int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy, int O, int ldgw,
                      int kh, int kw, int stride, int pad, int pixel_shuffle,

@@ -459,7 +459,15 @@ def _fprop_plan(*args):
     return (kernel,) + _PLANS.get(kernel, ("conv_fprop", None)) + (out[3] * args[8], out[4])
 
 
-_WGRAD_WS_CACHE: dict = {}
+@functools.lru_cache(maxsize=None)
+def _wgrad_plan(*geom):
+    """What the library runs for a weight gradient: msg_conv2d_wgrad_plan(*geom, MSG_WGRAD_K_AUTO) -- dtype .. per_sample as the
+    launch gets them, the K split left to the library -- asked once per tuple.  -> (workspace floats, K-slices in the grid).
+    A geometry the library refuses raises with its code."""
+    out = (ctypes.c_longlong * _lib.MSG_WPLAN_FIELDS)()
+    _lib.check(_lib.lib().msg_conv2d_wgrad_plan(*geom, _lib.MSG_WGRAD_K_AUTO, ctypes.addressof(out), len(out)),
+               "msg_conv2d_wgrad_plan")
+    return out[10], out[1]
 
 
 def _launch_fprop(x, wk, ck, bias, n, out_hw, kh, kw, stride, pad, in_up, pixel_shuffle, per_sample, c_real,
@@ -543,20 +551,6 @@ def _grad_dest(param):
     return grad_destination(param)
 
 
-def wgrad_k_chunks(b, o, i, taps, oh, ow, per_sample, kp):
-    """The K split _launch_wgrad asks msg_conv2d_wgrad for (kp: pixels per K-step, 64 bf16 / 32 fp32)."""
-    tiles = ((o + 127) // 128) * ((i + 127) // 128) * taps * b
-    if per_sample:
-        # one K sweep per (sample, tile, tap) unless that leaves most of the chip idle (the 512 -> 3 toRGB layers: 64
-        # workgroups); then the pixels are split into K-slices
-        return max(1, min((oh * ow) // (16 * kp), 1024 // tiles)) if tiles < 256 else 1
-    # (shared weights: the library folds the batch into K and picks the slice count; k_chunks only matters where it cannot)
-    k_chunks = max(1, min((oh * ow + 4 * kp - 1) // (4 * kp), (1024 + tiles - 1) // tiles))
-    while b * k_chunks > 65535:
-        k_chunks -= 1
-    return k_chunks
-
-
 def _launch_wgrad(gy, x, o, i, kh, kw, stride, pad, pixel_shuffle, per_sample, low_hw, raw=False, gain=1.0, out=None,
                   mode=None):
     """out: a contiguous fp32 tensor of o*i*kh*kw elements (the parameter's own layout) that receives a SHARED gradient."""
@@ -567,20 +561,14 @@ def _launch_wgrad(gy, x, o, i, kh, kw, stride, pad, pixel_shuffle, per_sample, l
     oh, ow = low_hw if pixel_shuffle else gv.shape[2:]
     taps = kh * kw
     ldgw = _round_up(i, 4)
-    k_chunks = wgrad_k_chunks(b, o, i, taps, oh, ow, per_sample, 64 if x.dtype == torch.bfloat16 else 32)
     geom = (_contraction_code(x, mode), b, ih, iw, cx, i, oh, ow, ldgy, o, ldgw, kh, kw, stride, pad, int(pixel_shuffle),
-            int(per_sample), k_chunks)
+            int(per_sample))
     # K-slices that add up to one result meet in a workspace of per-slice slabs and a fixed-order sum (deterministic; no
     # float atomics, no zero fill).  That sum also transposes a SHARED gradient into the parameter's own [O, I, kh, kw]
     # layout, so what autograd accumulates into the flat gradient bucket is a contiguous tensor; per-sample gradients and
     # unsplit results stay in the kernel's [O][tap][I] layout (128-byte runs; the parameter layout would scatter the
     # contraction kernel's stores: measured 25 % slower end to end) and the caller gets a strided view in parameter order.
-    need = _WGRAD_WS_CACHE.get(geom)                      # (a pure function of the geometry: one library call per distinct problem)
-    if need is None:
-        need = _lib.lib().msg_conv2d_wgrad_workspace(*geom)
-        if need < 0:
-            _lib.check(int(need), "msg_conv2d_wgrad_workspace")
-        _WGRAD_WS_CACHE[geom] = need
+    need, nz = _wgrad_plan(*geom)                         # (a pure function of the geometry: one library call per distinct problem)
     ws = _lib.scratch_ptr(need, dev) if need else None        # (launch-scoped: slabs -> the fixed-order sum of the same call)
     if per_sample or raw:
         out = None
@@ -595,10 +583,10 @@ def _launch_wgrad(gy, x, o, i, kh, kw, stride, pad, pixel_shuffle, per_sample, l
     key = "conv_wgrad"
     if _CLOCK_SHAPES and _lib.kernel_clock.enabled:
         key += f"|B{b} {ih}x{iw}->{oh}x{ow} {i}->{o} {kh}x{kw} s{stride}{' ps' if pixel_shuffle else ''}" \
-               f"{' per-sample' if per_sample else ' shared'}{f' slabs{need // (o * taps * ldgw)}' if need else ''}|"
+               f"{' per-sample' if per_sample else ' shared'}{f' slabs{nz}' if need else ''}|"
     with _lib.on_device(dev), _lib.kernel_clock.span((key, 'bf16' if x.dtype == torch.bfloat16 else 'f32'), flops):
         code = _lib.lib().msg_conv2d_wgrad(
-            gv.data_ptr(), xv.data_ptr(), gw.data_ptr(), *geom, int(oi_major), float(gain), ws, need,
+            gv.data_ptr(), xv.data_ptr(), gw.data_ptr(), *geom, _lib.MSG_WGRAD_K_AUTO, int(oi_major), float(gain), ws, need,
             _lib.stream_of(dev))
     _lib.check(code, "msg_conv2d_wgrad")
     if raw:

@@ -12,7 +12,10 @@
 // row3, generic; a WgradPlan is a value -- kernel, K split, logical rows, grid, workspace -- that the launch, the workspace query and
 // msg_conv2d_wgrad_plan all take from it.  `conv_wgrad_<k>_eligible(problem, WgradPlan*)` holds all of a kernel's conditions and
 // fills the plan; `conv_wgrad_<k>_launch(problem, plan, pointers, stream)` fills the kernel's parameter struct from the two and
-// cannot decline.  Both files take their K split from conv_wgrad_ksplit below.
+// cannot decline.  The K split is decided in this order: a k_chunks of MSG_WGRAD_K_AUTO becomes conv_wgrad_default_chunks (below)
+// in wgrad_plan_for, before anything reads it, so the kernel files only ever see a positive number; then each kernel's own model,
+// conv_wgrad_ksplit (below) with its constants, where that number has no say -- the row-sharing kernel when it is 1, and every
+// shared-weight problem whose batch folds into K.
 #pragma once
 #include "msg_common.h"
 
@@ -130,6 +133,27 @@ inline long long conv_wgrad_ksplit(long long steps, long long wgs, const WgradSp
         if (wgs * c > m.max_wgs) break;
     }
     return chunks;
+}
+
+// What MSG_WGRAD_K_AUTO stands for: the k_chunks the Python layer used to compute and pass, as it was (a rule of its own, not
+// conv_wgrad_ksplit: the plans of the models' layers depend on it).  The extents are positive here (wgrad_check).  0 for shared
+// weights over more than 65535 samples: MSG_EINVAL, as the caller's own 0 is.
+inline int conv_wgrad_default_chunks(const WgradProblem& q) {
+    const long long kp = q.dtype == MSG_BF16 ? 64 : 32, npix = (long long)q.OH * q.OW;      // pixels per K-step, per sample
+    // (128 x 128 tiles x taps x samples; counted up to 1024 -- every count from there on gives the same answers -- so that no
+    //  extent can overflow the product)
+    long long tiles = (long long)((q.O + 127ll) / 128) * ((q.I + 127ll) / 128);
+    for (const int n : {q.kh, q.kw, q.B}) tiles = tiles < 1024 ? tiles * n : 1024;
+    if (q.per_sample) {
+        // one K sweep per (sample, tile, tap) unless that leaves most of the chip idle (the 512 -> 3 toRGB layers: 64
+        // workgroups); then the pixels are split into K-slices
+        if (tiles >= 256) return 1;
+        return (int)std::max(1ll, std::min(npix / (16 * kp), 1024 / tiles));
+    }
+    // (shared weights: the batch is folded into K and the kernel's own model picks the slice count; this only matters where it cannot)
+    long long chunks = std::max(1ll, std::min((npix + 4 * kp - 1) / (4 * kp), (1024 + tiles - 1) / tiles));
+    while (q.B * chunks > 65535) --chunks;
+    return (int)chunks;
 }
 
 WgradPlan conv_wgrad_select(const WgradProblem& q);

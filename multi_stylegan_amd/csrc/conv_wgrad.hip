@@ -639,11 +639,14 @@ static WgradProblem wgrad_problem(int dtype, int B, int IH, int IW, int Cx, int 
 
 // The argument checks of the three entries, in the order their codes are promised: MSG_EINVAL before MSG_EUNSUPPORTED; the
 // pointers of a launch (`io`: gy, x, gw, ws; NULL for the queries) between the two.  An empty batch is MSG_OK whatever the rest.
-static int wgrad_check(const WgradProblem& q, const void* const* io) {
+// MSG_WGRAD_K_AUTO is resolved here, once the extents are known to be positive: from here on q.k_chunks is the number of K-slices.
+static int wgrad_check(WgradProblem& q, const void* const* io) {
     if (q.B == 0) return MSG_OK;
     if (q.B < 0 || q.IH <= 0 || q.IW <= 0 || q.OH <= 0 || q.OW <= 0 || q.O <= 0 || q.I <= 0 || q.kh <= 0 || q.kw <= 0 ||
-        q.stride <= 0 || q.Cx <= 0 || q.ldgy <= 0 || q.ldgw < q.I || q.ldgw % 4 || q.k_chunks <= 0)
+        q.stride <= 0 || q.Cx <= 0 || q.ldgy <= 0 || q.ldgw < q.I || q.ldgw % 4)
         return MSG_EINVAL;
+    if (q.k_chunks == MSG_WGRAD_K_AUTO) q.k_chunks = conv_wgrad_default_chunks(q);
+    if (q.k_chunks <= 0) return MSG_EINVAL;
     if (io && (!io[0] || !io[1] || !io[2])) return MSG_EINVAL;
     if (q.dtype != MSG_F32 && q.dtype != MSG_BF16) return MSG_EUNSUPPORTED;
     const int vec = 16 / q.esz();
@@ -652,8 +655,8 @@ static int wgrad_check(const WgradProblem& q, const void* const* io) {
     return MSG_OK;
 }
 
-// checks + selection: MSG_OK and the plan, or the code of a call that stops before the plan is used
-static int wgrad_plan_for(const WgradProblem& q, const void* const* io, WgradPlan* plan) {
+// checks (which resolve q.k_chunks) + selection: MSG_OK and the plan, or the code of a call that stops before the plan is used
+static int wgrad_plan_for(WgradProblem& q, const void* const* io, WgradPlan* plan) {
     const int rc = wgrad_check(q, io);
     if (rc != MSG_OK) return rc;
     *plan = conv_wgrad_select(q);
@@ -663,9 +666,10 @@ static int wgrad_plan_for(const WgradProblem& q, const void* const* io, WgradPla
 extern "C" long long msg_conv2d_wgrad_workspace(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy,
                                                 int O, int ldgw, int kh, int kw, int stride, int pad, int pixel_shuffle,
                                                 int per_sample, int k_chunks) {
+    WgradProblem q = wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle, per_sample,
+                                   k_chunks, 0, 1.f);
     WgradPlan plan;
-    const int rc = wgrad_plan_for(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
-                                                per_sample, k_chunks, 0, 1.f), nullptr, &plan);
+    const int rc = wgrad_plan_for(q, nullptr, &plan);
     return rc == MSG_OK ? plan.need : (long long)rc;
 }
 
@@ -673,9 +677,10 @@ extern "C" long long msg_conv2d_wgrad_workspace(int dtype, int B, int IH, int IW
 extern "C" int msg_conv2d_wgrad_plan(int dtype, int B, int IH, int IW, int Cx, int I, int OH, int OW, int ldgy,
                                      int O, int ldgw, int kh, int kw, int stride, int pad, int pixel_shuffle,
                                      int per_sample, int k_chunks, long long* out, int n_out_fields) {
+    WgradProblem q = wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle, per_sample,
+                                   k_chunks, 0, 1.f);
     WgradPlan plan;
-    const int rc = wgrad_plan_for(wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle,
-                                                per_sample, k_chunks, 0, 1.f), nullptr, &plan);
+    const int rc = wgrad_plan_for(q, nullptr, &plan);
     if (rc != MSG_OK) return rc;
     const long long fields[MSG_WPLAN_FIELDS] = {plan.kernel, plan.nz, plan.chunks_per_out, plan.n_out, plan.slice_pixels, plan.OWv,
                                                 plan.OHv, plan.fold, plan.xcd_slices, plan.blocks, plan.need};
@@ -688,8 +693,8 @@ extern "C" int msg_conv2d_wgrad(const void* gy, const void* x, float* gw, int dt
                                 int kh, int kw, int stride, int pad, int pixel_shuffle,
                                 int per_sample, int k_chunks, int oi_major, float gain,
                                 float* ws, long long ws_floats, void* stream) {
-    const WgradProblem q = wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle, per_sample,
-                                         k_chunks, oi_major, gain);
+    WgradProblem q = wgrad_problem(dtype, B, IH, IW, Cx, I, OH, OW, ldgy, O, ldgw, kh, kw, stride, pad, pixel_shuffle, per_sample,
+                                   k_chunks, oi_major, gain);
     const void* const io[4] = {gy, x, gw, ws};
     WgradPlan plan;
     int rc = wgrad_plan_for(q, io, &plan);

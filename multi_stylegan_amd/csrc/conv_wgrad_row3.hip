@@ -356,7 +356,8 @@ bool conv_wgrad_row3_eligible(const WgradProblem& q, WgradPlan* plan) {
     const long long tiles = (long long)((q.O + 127) / 128) * ((q.I + 127) / 128) * q.kh;
     long long steps_per_chunk, chunks;
     if (q.per_sample) {
-        // the caller's k_chunks, or -- when it has no opinion (1) -- the wave-quantisation model of conv_wgrad_ksplit over this
+        // q.k_chunks -- the caller's, or under MSG_WGRAD_K_AUTO the default rule's (conv_wgrad_default_chunks, resolved before
+        // this function runs) -- or, when that has no opinion (1), the wave-quantisation model of conv_wgrad_ksplit over this
         // kernel's ONE workgroup per CU: B * tiles workgroups in rounds of 256.  Batch 16 x 512 -> 512 is 768 workgroups = three
         // full rounds; batch 8 (the path-length pass works on half a batch) is 384 = one and a half, i.e. a quarter of the
         // launch on half-empty hardware (round 5: 1 101 TFLOP/s against 1 352 at batch 16); two K-slices per sample make it

@@ -187,10 +187,8 @@ def test_weight_gradient_plan_branches(case):
     x = torch.randn(b, i, h, w_, generator=g).to(dtype)
     gy = torch.randn(b, o, *((2 * h, 2 * w_) if shuffle else (h, w_)), generator=g).to(dtype)
     # the geometry _launch_wgrad passes, asked of the plan query first
-    kp = 64 if dtype == torch.bfloat16 else 32
     code = {None: _lib.MSG_BF16, "exact": _lib.MSG_F32, "split_bf16x3": _lib.MSG_F32_SPLIT}[mode]
-    geom = (code, b, h, w_, i, i, h, w_, o, o, i, k, k, 1, pad, int(shuffle), int(per_sample),
-            conv_ops.wgrad_k_chunks(b, o, i, k * k, h, w_, per_sample, kp))
+    geom = (code, b, h, w_, i, i, h, w_, o, o, i, k, k, 1, pad, int(shuffle), int(per_sample), _lib.MSG_WGRAD_K_AUTO)
     out = (ctypes.c_longlong * _lib.MSG_WPLAN_FIELDS)()
     assert _lib.lib().msg_conv2d_wgrad_plan(*geom, ctypes.addressof(out), len(out)) == _lib.MSG_OK
     plan = dict(zip(("kernel", "nz", "chunks_per_out", "n_out", "slice_pixels", "OWv", "OHv", "fold", "xcd_slices", "blocks", "need"), out))
@@ -210,6 +208,38 @@ def test_weight_gradient_plan_branches(case):
                                 mode=mode)
     assert gw.shape == gw_r.shape
     assert rel_err(gw, gw_r) < TOLS[dtype], (name, rel_err(gw, gw_r))
+
+
+@pytest.mark.parametrize("case", PLAN_BRANCHES, ids=[c[0] for c in PLAN_BRANCHES])
+def test_weight_gradient_auto_split_runs_the_rules_plan(case):
+    """msg_conv2d_wgrad with k_chunks = MSG_WGRAD_K_AUTO against the same call with the number the Python layer used to pass
+    (tools/gen_dispatch_table.py: model_k_chunks), per branch of the plan: the same plan and the same fixed-order sum, so the same
+    bits and the same workspace size.  Kernel layout, oi_major = 0, gain 1; outputs pre-filled with NaN."""
+    from multi_stylegan_amd import _lib
+    from tools.gen_dispatch_table import model_k_chunks
+    name, dtype, mode, per_sample, h, w_, k, shuffle, _gain, _expect = case
+    b, i, o = 2, 64, 64
+    pad = 0 if shuffle else k // 2
+    g = torch.Generator().manual_seed(len(name) * 17)
+    cl = lambda t: t.to(DEV).contiguous(memory_format=torch.channels_last)
+    x = cl(torch.randn(b, i, h, w_, generator=g).to(dtype))
+    gy = cl(torch.randn(b, o, *((2 * h, 2 * w_) if shuffle else (h, w_)), generator=g).to(dtype))
+    code = {None: _lib.MSG_BF16, "exact": _lib.MSG_F32, "split_bf16x3": _lib.MSG_F32_SPLIT}[mode]
+    geom = (code, b, h, w_, i, i, h, w_, o, o, i, k, k, 1, pad, int(shuffle), int(per_sample))
+    results, needs = [], []
+    for k_chunks in (_lib.MSG_WGRAD_K_AUTO,
+                     model_k_chunks(b, o, i, k * k, h, w_, int(per_sample), 64 if dtype == torch.bfloat16 else 32)):
+        need = _lib.lib().msg_conv2d_wgrad_workspace(*geom, k_chunks)
+        assert need >= 0
+        ws = torch.empty(max(need, 4), dtype=torch.float32, device=DEV)
+        gw = torch.full((b if per_sample else 1, o, k * k, i), float("nan"), dtype=torch.float32, device=DEV)
+        assert _lib.lib().msg_conv2d_wgrad(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), *geom, k_chunks, 0, 1.0, ws.data_ptr(), need,
+                                           _lib.stream_of(torch.device(DEV))) == _lib.MSG_OK
+        torch.cuda.synchronize()
+        results.append(gw)
+        needs.append(need)
+    assert needs[0] == needs[1]
+    assert not torch.isnan(results[0]).any() and torch.equal(results[0], results[1])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

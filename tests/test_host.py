@@ -580,6 +580,78 @@ def test_weight_gradient_codes_before_any_launch():
         assert lib.msg_conv2d_wgrad_workspace(*changed(1, 0)) == 0 and wgrad_plan(lib, changed(1, 0)) == [0] * _lib.MSG_WPLAN_FIELDS
 
 
+def test_weight_gradient_auto_split_is_the_python_rule():
+    """k_chunks = MSG_WGRAD_K_AUTO is the rule the Python layer used to compute and pass (tools/gen_dispatch_table.py keeps it,
+    frozen, as model_k_chunks): over every row of the weight-gradient grid on which that rule gives a split, the plan and the
+    workspace under AUTO are those under the rule's number -- every field, or the code -- and on the models' rows, which the grid
+    builds with that number, they are therefore the recorded answers too.  Then the corners by direct queries (no launch runs)."""
+    from multi_stylegan_amd import _lib
+    from multi_stylegan_amd.build import build
+    from tools import gen_dispatch_table as grid
+    build(verbose=False)
+    lib = _lib.lib()
+    AUTO, OK, EINVAL, EUNSUPPORTED = _lib.MSG_WGRAD_K_AUTO, _lib.MSG_OK, _lib.MSG_EINVAL, _lib.MSG_EUNSUPPORTED
+    assert AUTO == -1
+    with open(os.path.join(GOLDEN, "dispatch_table.json")) as f:
+        table = json.load(f)
+
+    def rule(r):                 # dtype B IH IW Cx I OH OW ldgy O ldgw kh kw stride pad shuffle per_sample [k_chunks]
+        return grid.model_k_chunks(r[1], r[9], r[5], r[11] * r[12], r[6], r[7], r[16], 64 if r[0] == _lib.MSG_BF16 else 32)
+
+    rows = grid.wgrad_plan_rows()
+    n_ws = len(grid.wgrad_rows())                                      # (the workspace table is the first rows of the plan table)
+    assert len(rows) == len(table["wgrad_plan"]) and grid.digest(rows) == table["digest"]["wgrad_plan"]
+    compared, recorded = 0, set()
+    for n, r in enumerate(rows):
+        if r[1] < 1 or min(r[2], r[3], r[5], r[6], r[7], r[9], r[11], r[12]) < 1 or rule(r) < 1:
+            continue
+        kc, auto = rule(r), r[:17] + [AUTO]
+        assert grid.wgrad_plan(lib, auto) == grid.wgrad_plan(lib, r[:17] + [kc]), (r, kc)
+        assert lib.msg_conv2d_wgrad_workspace(*auto) == lib.msg_conv2d_wgrad_workspace(*r[:17], kc), (r, kc)
+        compared += 1
+        if kc == r[17]:                                                # the row IS the rule's call: the recorded answer
+            assert grid.wgrad_plan(lib, auto) == table["wgrad_plan"][n], (r, kc)
+            assert n >= n_ws or lib.msg_conv2d_wgrad_workspace(*auto) == table["wgrad_workspace"][n], (r, kc)
+            recorded.add(n)
+    # the rows wgrad_rows() builds with model_k_chunks -- per (batch, shared / per-sample): the 'same' convs of LAYERS at 1x1 and
+    # 3x3, the stride-2 convs, the up-convolutions, then four groups of three thin layers of which the first has it -- all did
+    per_block = [2 * sum(len(sizes) for _i, _o, sizes in grid.LAYERS) + sum(len(sizes) for _c, sizes in grid.STRIDE2) +
+                 len(grid.SIZES) - 1, 3 * 4]
+    model = {blk * sum(per_block) + k for blk in range(2 * len(grid.BATCHES)) for k in range(sum(per_block))
+             if k < per_block[0] or (k - per_block[0]) % 3 == 0}
+    assert len(model) == 2 * len(grid.BATCHES) * (per_block[0] + 4) and max(model) < n_ws
+    assert all(rows[n][0] == _lib.MSG_BF16 and rows[n][17] == rule(rows[n]) for n in model)
+    assert model <= recorded and compared >= len(recorded), (compared, len(recorded), len(model))
+    assert any(rows[n][17] > 1 for n in model if rows[n][16]) and any(rows[n][17] > 1 for n in model if not rows[n][16])
+
+    bf16 = _lib.MSG_BF16
+    gy, x, gw, ws = 0x10000, 0x20000, 0x30000, 0x40000                  # fake, 16-byte aligned: every call returns before using one
+
+    def answers(geom):           # the plan query, the workspace query, and the launch (a code only where it stops before a launch)
+        return (grid.wgrad_plan(lib, geom), lib.msg_conv2d_wgrad_workspace(*geom),
+                lib.msg_conv2d_wgrad(gy, x, gw, *geom, 0, 1.0, ws, 1 << 40, None))
+    # shared weights that cannot fold (B * pixels = 2^31): the only place the shared-weight number reaches the kernel
+    big = [bf16, 16384, 512, 256, 64, 64, 512, 256, 64, 64, 64, 1, 1, 1, 0, 0, 0]
+    kc = grid.model_k_chunks(16384, 64, 64, 1, 512, 256, 0, 64)
+    plan = grid.wgrad_plan(lib, big + [AUTO])
+    assert kc >= 1 and plan == grid.wgrad_plan(lib, big + [kc]) and isinstance(plan, list)
+    assert plan[7] == 0 and plan[1] == 16384 * kc and plan[2] == plan[1]                 # not folded: k_chunks slices per sample
+    assert lib.msg_conv2d_wgrad_workspace(*big, AUTO) == lib.msg_conv2d_wgrad_workspace(*big, kc) == plan[10] > 0
+    # shared weights over more than 65535 samples: the rule's loop ends at 0 slices -- MSG_EINVAL, as through the Python layer before
+    many = [bf16, 65536, 4, 4, 64, 64, 4, 4, 64, 64, 64, 1, 1, 1, 0, 0, 0]
+    assert grid.model_k_chunks(65536, 64, 64, 1, 4, 4, 0, 64) == 0
+    assert answers(many + [AUTO]) == (EINVAL, EINVAL, EINVAL)
+    assert isinstance(grid.wgrad_plan(lib, many + [1]), list)                            # (the caller's own number is taken)
+    small = [bf16, 2, 8, 64, 64, 64, 8, 64, 64, 64, 64, 3, 3, 1, 1, 0, 0]
+    changed = lambda index, value: small[:index] + [value] + small[index + 1:]
+    assert isinstance(grid.wgrad_plan(lib, small + [AUTO]), list)
+    assert answers(changed(1, 0) + [AUTO]) == ([0] * _lib.MSG_WPLAN_FIELDS, 0, OK)        # an empty batch
+    assert answers(small + [-2]) == (EINVAL, EINVAL, EINVAL) and answers(small + [0]) == (EINVAL, EINVAL, EINVAL)
+    assert answers(changed(10, 60) + [AUTO]) == (EINVAL, EINVAL, EINVAL)                 # ldgw < I
+    assert answers(changed(4, 60) + [AUTO]) == (EUNSUPPORTED, EUNSUPPORTED, EUNSUPPORTED)   # Cx: no whole 16-byte vectors
+    assert answers(changed(4, 60)[:10] + [60, 3, 3, 1, 1, 0, 0, AUTO]) == (EINVAL, EINVAL, EINVAL)   # ... MSG_EINVAL first
+
+
 def test_forward_codes_before_any_launch():
     """What msg_conv2d_fprop, msg_conv2d_fprop_act_mask and msg_conv2d_fprop_act_backward answer without reaching a launch, on a
     geometry of the row-sharing kernel and one of the ping-pong kernel: the codes the commit before fprop_check / fprop_plan_for

@@ -166,9 +166,16 @@ def thin_rows():
 
 
 def model_k_chunks(b, o, i, taps, oh, ow, per_sample, kp=64):
-    """The K split conv_ops._launch_wgrad asks for (bf16: 64 pixels per K-step)."""
-    from multi_stylegan_amd.conv_ops import wgrad_k_chunks
-    return wgrad_k_chunks(b, o, i, taps, oh, ow, per_sample, kp)
+    """The K split the Python layer passed for the models' layers when the table was recorded (kp: pixels per K-step, 64 bf16 /
+    32 fp32) -- the rule the recorded rows were built with, frozen here: NOT to be edited.  The library's MSG_WGRAD_K_AUTO
+    (conv_wgrad_default_chunks, csrc/conv_dispatch.h) must give the same number; tests/test_host.py holds it to that."""
+    tiles = ((o + 127) // 128) * ((i + 127) // 128) * taps * b
+    if per_sample:
+        return max(1, min((oh * ow) // (16 * kp), 1024 // tiles)) if tiles < 256 else 1
+    k_chunks = max(1, min((oh * ow + 4 * kp - 1) // (4 * kp), (1024 + tiles - 1) // tiles))
+    while b * k_chunks > 65535:
+        k_chunks -= 1
+    return k_chunks
 
 
 def missing_profile_geometries(paths):
@@ -201,7 +208,7 @@ def wgrad_rows():
 
     for b in BATCHES:
         for ps in (0, 1):
-            # (the models' rows carry the k_chunks conv_ops._launch_wgrad computes for them: model_k_chunks)
+            # (the models' rows carry the k_chunks the library's MSG_WGRAD_K_AUTO stands for on them: model_k_chunks)
             for cin, cout, sizes in LAYERS:
                 for r in sizes:
                     for k in (1, 3):
