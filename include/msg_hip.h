@@ -757,6 +757,53 @@ long long msg_elastic_workspace(int B, int H, int W);
 int msg_elastic_deform(const void* in, const float* noise, float* field, void* out, int dtype,
                        int B, int F, int H, int W, int sigma, float alpha, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Baseline JPEG (ITU T.81: sequential DCT, Huffman, 8 bit), 4:2:0, for a batch of pictures: from the interleaved RGB bytes
+ * msg_sample_sheet writes to the entropy-coded scan of every frame, so that the compressed stream and not 3 B per pixel goes to
+ * the host.  Replaces the PNG frame directory and the ffmpeg call of scripts/gan_latent_space_interpolation.py:57-59; the host
+ * adds the headers and the container (multi_stylegan_amd/video.py).
+ * rgb      [N, H, W, 3] bytes, any alignment; any H, W >= 1
+ * qtables  [2][64] on the HOST (read during the call, passed to the kernels by value): luma then chroma, natural (row-major)
+ *          order, every entry 1 .. 255
+ * coef     NULL, or [N, MR, MC, 6, 64] 16-bit (2-byte aligned), every element written: per MCU the blocks Y00, Y01, Y10, Y11,
+ *          Cb, Cr, each in zigzag order, quantised, DC not yet differenced
+ * scan     as many bytes as msg_jpeg_scan_capacity(N, H, W, &bytes) says, any alignment; scan[offsets[n] .. offsets[n + 1]) is frame n's complete
+ *          entropy-coded segment, what stands between the SOS header and EOI.  Frames are dense, one after the other.  Bytes at
+ *          and past offsets[N] are not written.
+ * offsets  [N + 1] (8-byte aligned), all written; offsets[0] = 0
+ * ws       msg_jpeg_workspace(N, H, W) BYTES, 16-byte aligned: the coefficients, one slot of bytes per restart interval, the
+ *          intervals' lengths and starts.  Needs no initialisation and carries nothing between calls.  The capacity and the
+ *          slots are sized for the longest stream the tables can produce (208 B per block, every byte stuffed): 2496 B per MCU,
+ *          3.25 x the RGB bytes, of which a sheet touches a few per cent.
+ * Geometry: an MCU is 16 x 16 pixels, MR = ceil(H / 16), MC = ceil(W / 16); pixels outside the picture repeat its last row or
+ * column.
+ * Colour (JFIF, full range), in fp32 from the bytes: Y = 0.299 R + 0.587 G + 0.114 B, Cb = -0.168736 R - 0.331264 G + 0.5 B + 128,
+ * Cr = 0.5 R - 0.418688 G - 0.081312 B + 128; 128 is subtracted from each of the three; a chroma sample is the mean of its 2 x 2
+ * pixels, taken in float (no rounding to bytes in between).
+ * Transform: the 8 x 8 DCT-II of T.81 A.3.3, F(v, u) = 1/4 C(u) C(v) sum_y sum_x f(y, x) cos((2x + 1) u pi / 16)
+ * cos((2y + 1) v pi / 16), C(0) = 1 / sqrt 2, evaluated separably in fp32 (rows, then columns).
+ * Quantisation: q = sign(c) floor(|c| / Q + 1/2); AC clamped to +-1023 and the DC difference to +-2047, the ranges the Annex K
+ * tables code.
+ * Scan: the four Huffman tables of T.81 Annex K.3 (K.3 / K.5 for Y, K.4 / K.6 for Cb and Cr); one restart interval is one MCU
+ * row (Ri = MC) and DC prediction starts from 0 in each; every interval is padded to a byte with 1-bits and RSTm, FF D0+(r mod 8),
+ * follows interval r of a frame except its last; every FF the coder produces is followed by 00.
+ * Four launches (transform and quantise; code one interval per workgroup, the bits assembled in LDS; prefix sum of the N MR
+ * interval lengths; pack), no synchronisation, nothing read back.  Bit-identical from run to run, and a frame's bytes do not
+ * depend on the rest of the batch: the only atomics are ORs into LDS words.
+ * msg_jpeg_scan_capacity writes the byte count to *bytes (host memory) and returns a status like every entry that is not a
+ * workspace size; msg_jpeg_workspace returns -1, and the capacity query MSG_EINVAL, for sizes the entry refuses with MSG_EINVAL.
+ * MSG_EINVAL: a NULL pointer other than coef, a misaligned ws / coef / offsets, a non-positive size, a table entry outside
+ * 1 .. 255, N or MR above 65535, N MR above 2^31 - 1, byte counts that do not fit 63 bits.
+ * MSG_EUNSUPPORTED: W > MSG_JPEG_MAX_WIDTH.  The interval coder walks an interval in chunks of 256 blocks, so its LDS buffer
+ * bounds the chunk and not the width; the limit keeps an interval's slot (and the 32-bit byte counts within it) below 2^23.
+ * Nothing is launched in any of these cases.
+ * ------------------------------------------------------------------------- */
+#define MSG_JPEG_MAX_WIDTH 16384
+long long msg_jpeg_workspace(int N, int H, int W);
+int msg_jpeg_scan_capacity(int N, int H, int W, long long* bytes);
+int msg_jpeg_encode(const unsigned char* rgb, const unsigned short* qtables, short* coef, unsigned char* scan,
+                    long long* offsets, int N, int H, int W, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

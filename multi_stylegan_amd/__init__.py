@@ -17,6 +17,7 @@ from .samples import (SheetWriter, dump_samples, epoch_sample_dump, interpolatio
                       save_prediction, write_png)
 from .tlfm_dataset import TFLMDatasetGAN, read_tiff
 from .validation_metrics import FID, FVD, IS
+from .video import MjpegWriter, interpolation_video, jpeg_encode, jpeg_file, jpeg_tables
 
 __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper", "Draws", "PathLengthRegularization",
            "TopK", "AdaptiveDiscriminatorAugmentation", "AugmentationPipeline", "GeneratorSampler", "load_generator_ema", "split_sequences", "validation_samples",
@@ -25,4 +26,5 @@ __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper
            "interpolation_frames", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters",
            "WassersteinDiscriminatorLoss", "WassersteinDiscriminatorLossCutMix", "WassersteinGeneratorLoss", "HingeGeneratorLoss",
            "HingeDiscriminatorLoss", "HingeDiscriminatorLossCutMix", "R2Regularization", "ElasticDeformation", "elastic_deformation",
-           "elastic_deform_batch", "ResidentTLFMStore", "ResidentTLFMFeed", "gather_tlfm_batch"]
+           "elastic_deform_batch", "ResidentTLFMStore", "ResidentTLFMFeed", "gather_tlfm_batch", "jpeg_tables", "jpeg_encode", "jpeg_file",
+           "MjpegWriter", "interpolation_video"]

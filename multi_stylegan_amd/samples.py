@@ -11,7 +11,7 @@ the host as fp32 RGB planes (12 B per pixel, synchronously) and quantised and PN
 * ``SheetWriter`` moves the uint8 sheets through a ring of pinned buffers on a copy stream and encodes them on worker threads
   while the generator already produces the next batch;
 * ``save_prediction`` / ``epoch_sample_dump`` / ``dump_samples`` / ``interpolation_frames`` are the three outputs, with the
-  reference's file names.  Video encoding stays outside (INTEGRATION.md shows the ffmpeg command for the frames).
+  reference's file names.  The interpolation as a video, encoded on the device: video.py.
 
 Command line: ``python -m multi_stylegan_amd.samples samples|interpolate --load_checkpoint F --out DIR ...``.
 """
