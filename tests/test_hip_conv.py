@@ -4,11 +4,13 @@ geometry of the path, shared and per-sample weights, ragged channel counts and t
 f32 path = exact-fp32 MFMA: 1e-4 of max|ref| (BASELINE tolerance is 1e-3);  bf16 storage: 2e-2."""
 import math
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from conv_kernel_cases import BY_NAME, CASES as LARGE_TILE_CASES, EPILOGUE_CASES
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -603,7 +605,15 @@ def test_modulated_conv_random_geometries(case):
         assert (a.float() - r.float()).norm() / (r.float().norm() + 1e-12) < tol, nm
 
 
-PP_CASES = [  # shapes that take the 256x256 ping-pong kernel: name, kind, B, I, O, H, W, k, stride, pad, per_sample
+# name, kind, B, I, O, H, W, k, stride, pad, per_sample.  Named for the 256 x 256 ping-pong kernel and the row-sharing kernels they
+# were written for; since those kernels decline grids that do not fill the chip (224 workgroups on the 256 tile, 448 on the 128 row-
+# sharing tile) most of them run elsewhere, bf16, forward / data gradient:
+#   pp_*: the 128 x 128 kernels (LDS-DMA or register staging), both directions -- none reaches conv_fprop_pp;
+#   row3_256w_ps_192, row3_256w_shared_256: forward on the 256 row-sharing tile (the second: its data gradient too);
+#   row3_512w_ps, row3_narrow_384: forward on the 128 row-sharing tile;  the other eight row3_*: the 128 x 128 LDS-DMA kernel.
+# They stay as tests of those kernels against float64.  The shapes that do reach the large tiles, and say so, are in
+# tests/conv_kernel_cases.py (test_large_tile_kernels_against_float64 below).
+PP_CASES = [
     ("pp_3x3_ragged_m", "conv", 5, 64, 256, 15, 15, 3, 1, 1, True),            # per-sample M = 225 (< tile), many z
     ("pp_3x3_shared", "conv", 4, 72, 384, 40, 40, 3, 1, 1, False),              # N tail (384), ragged K (72)
     ("pp_1x1_shared", "conv", 8, 256, 256, 48, 48, 1, 1, 0, False),
@@ -631,7 +641,7 @@ PP_CASES = [  # shapes that take the 256x256 ping-pong kernel: name, kind, B, I,
 
 @pytest.mark.parametrize("case", PP_CASES, ids=[c[0] for c in PP_CASES])
 def test_pingpong_kernel_shapes(case):
-    """bf16 forward + data gradient on shapes large enough for conv_fprop_pp.hip, against fp64 CPU convolutions."""
+    """bf16 forward + data gradient against fp64 CPU convolutions, on whichever kernel takes the shape (see PP_CASES)."""
     from multi_stylegan_amd import conv_ops
     name, kind, b, i, o, h, w_, k, stride, pad, per_sample = case
     g = torch.Generator().manual_seed(len(name))
@@ -649,6 +659,100 @@ def test_pingpong_kernel_shapes(case):
     gx, = torch.autograd.grad(y, xd, gy.to(DEV, torch.bfloat16).contiguous(memory_format=torch.channels_last))
     assert rel_err(y.float(), yr) < 2e-2, "forward"
     assert rel_err(gx.float(), gxr) < 2e-2, "data gradient"
+
+
+def _worst_element(got, ref):
+    """(sample, channel, row, column) of the largest |got - ref|, and the two values there: which tile or halo row is wrong."""
+    diff = (got.double().cpu() - ref).abs()
+    at = tuple(int(v) for v in np.unravel_index(int(diff.argmax()), diff.shape))
+    return {"worst (sample, channel, row, column)": at, "got": float(got[at]), "want": float(ref[at])}
+
+
+def _clocked(fn, want_kernel):
+    """fn() with the kernel clock on: its result, after asserting that the ONE launch of the forward family it made carries the
+    clock label of the MSG_PLAN_* kernel named `want_kernel` (conv_ops._PLANS)."""
+    from multi_stylegan_amd import _lib, conv_ops
+    _lib.kernel_clock.reset(enabled=True)
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        ran = {key: v["launches"] for key, v in _lib.kernel_clock.summary().items() if key.startswith("conv_fprop")}
+    finally:
+        _lib.kernel_clock.reset(enabled=False)
+    label = conv_ops._PLANS[getattr(_lib, "MSG_PLAN_" + want_kernel)][0]
+    assert ran == {label + "/bf16": 1}, (want_kernel, ran)
+    return out
+
+
+def _large_tile_operands(c):
+    """bf16-exact float64 operands of a case of tests/conv_kernel_cases.py, from a generator seeded by its name."""
+    g = torch.Generator().manual_seed(sum(ord(ch) for ch in c.name))
+    x = torch.randn(c.B, c.I, c.H, c.W, generator=g).bfloat16().double()
+    wshape = (c.B, c.O, c.I, c.k, c.k) if c.per_sample else (c.O, c.I, c.k, c.k)
+    w = (torch.randn(*wshape, generator=g) / math.sqrt(c.I * c.k * c.k)).bfloat16().double()
+    return g, x, w
+
+
+@pytest.mark.parametrize("case", LARGE_TILE_CASES, ids=[c.name for c in LARGE_TILE_CASES])
+def test_large_tile_kernels_against_float64(case):
+    """The 256 x 256 ping-pong kernel and the row-sharing 3x3 kernels on both tiles (conv_fprop_pp.hip, conv_fprop_row3.hip), on the
+    smallest shapes their minimum-grid rules let through (tests/conv_kernel_cases.py; tests/test_host.py asserts the table against
+    the plan query): bf16 forward and data gradient of bf16-exact operands against float64 CPU convolutions, 2e-2 of max|ref|.  The
+    kernel-clock label of each of the two launches must be the kernel the case names -- which also checks the table's own mirror of
+    the data-gradient launch -- so a case cannot drift to another kernel unnoticed."""
+    from multi_stylegan_amd import conv_ops
+    c, tol = case, TOLS[torch.bfloat16]
+    g, x, w = _large_tile_operands(c)
+    xr = x.clone().requires_grad_(True)
+    yr = _reference(c.kind, xr, w, c.stride, c.pad, c.per_sample)
+    gy = torch.randn(yr.shape, generator=g).bfloat16().double()
+    gxr, = torch.autograd.grad(yr, xr, gy)
+    yr = yr.detach()
+    xd = x.to(DEV, torch.bfloat16).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    wd = w.to(DEV, torch.float32)
+    gyd = gy.to(DEV, torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    geo = conv_ops.Geometry(c.kind, c.k, c.k, c.stride if c.kind == "conv" else 1, c.pad, (c.H, c.W), c.per_sample)
+    y = _clocked(lambda: conv_ops._ConvF.apply(xd, wd, None, geo), c.fwd)
+    gx, = _clocked(lambda: torch.autograd.grad(y, xd, gyd), c.dgrad)
+    assert y.shape == yr.shape and y.dtype == torch.bfloat16 and gx.shape == x.shape
+    e_y, e_gx = rel_err(y.float(), yr), rel_err(gx.float(), gxr)
+    print(f"\n{c.name}: forward {c.fwd} rel_err {e_y:.3e}, data gradient {c.dgrad} rel_err {e_gx:.3e} (bound {tol:g})")
+    assert e_y < tol, ("forward", e_y, _worst_element(y.detach().float(), yr))
+    assert e_gx < tol, ("data gradient", e_gx, _worst_element(gx.float(), gxr))
+
+
+@pytest.mark.parametrize("name", EPILOGUE_CASES)
+def test_large_tile_kernel_epilogues_against_float64(name):
+    """The epilogue legs of the large-tile kernels at one floor shape each (ping-pong, row-sharing 256 and 128 tile), each against its
+    float64 form at 2e-2 of max|ref|, each launch under the kernel's clock label: the bias (conv_ops.conv2d), the fused activation
+    leaky_relu(conv + bias + noise * w, 0.2) * sqrt 2 with a per-sample noise map, and the residual merge (conv + map) * gain."""
+    from multi_stylegan_amd import conv_ops
+    c, tol = BY_NAME[name], TOLS[torch.bfloat16]
+    assert c.kind == "conv" and c.stride == 1 and not c.per_sample
+    g, x, w = _large_tile_operands(c)
+    conv = F.conv2d(x, w, padding=c.pad)
+    bias = torch.randn(c.O, generator=g)
+    noise = torch.randn(c.B, 1, *conv.shape[2:], generator=g)
+    noise_w = torch.tensor([0.37])
+    other = torch.randn(conv.shape, generator=g).bfloat16()
+    gain = 1 / math.sqrt(2)
+    xd = x.to(DEV, torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    wd = w.to(DEV, torch.float32)
+    geo = conv_ops.Geometry("conv", c.k, c.k, 1, c.pad, (c.H, c.W), False)
+    legs = {
+        "bias": (lambda: conv_ops.conv2d(xd, wd, bias.to(DEV), stride=1, padding=c.pad),
+                 conv + bias.double().view(1, -1, 1, 1)),
+        "fused activation": (lambda: conv_ops._f_raw(xd, wd, None, geo, act=(bias.to(DEV), noise.to(DEV), noise_w.to(DEV), 0.2, math.sqrt(2))),
+                             F.leaky_relu(conv + bias.double().view(1, -1, 1, 1) + noise.double() * noise_w.double(), 0.2) * math.sqrt(2)),
+        "residual": (lambda: conv_ops._f_raw(xd, wd, None, geo, residual=(other.to(DEV).contiguous(memory_format=torch.channels_last), gain)),
+                     (conv + other.double()) * gain),
+    }
+    for leg, (run, ref) in legs.items():
+        y = _clocked(run, c.fwd)
+        assert y.shape == ref.shape and y.dtype == torch.bfloat16
+        e = rel_err(y.float(), ref)
+        print(f"\n{c.name}: {leg} {c.fwd} rel_err {e:.3e} (bound {tol:g})")
+        assert e < tol, (leg, e, _worst_element(y.float(), ref))
 
 
 @pytest.mark.parametrize("b", [31, 33], ids=["just_below_2GiB", "above_2GiB"])
@@ -733,22 +837,25 @@ def test_grouped_linear_matches_per_layer(g, b, l, n, k):
         assert rel_err(a, c) < 1e-5
 
 
-@pytest.mark.parametrize("shape", [(4, 512, 512, 64, 64, 3, True), (2, 256, 256, 128, 128, 3, False),
-                                    (2, 128, 512, 32, 256, 3, True), (2, 192, 512, 64, 256, 3, True), (4, 256, 256, 48, 48, 1, False),
-                                    (2, 128, 128, 128, 128, 3, False), (8, 64, 256, 16, 512, 3, True),
-                                    (8, 128, 128, 128, 256, 3, False), (16, 64, 384, 64, 64, 3, False),
-                                    (32, 768, 768, 32, 32, 3, False)])
+# B, I, O, H, W, k, per-sample weights, and the kernel the shape takes today (bf16 forward).  The last two are the ping-pong kernel's
+@pytest.mark.parametrize("shape", [(4, 512, 512, 64, 64, 3, True, "DMA"), (2, 256, 256, 128, 128, 3, False, "DMA"),
+                                    (2, 128, 512, 32, 256, 3, True, "ROW3N"), (2, 192, 512, 64, 256, 3, True, "ROW3"),
+                                    (4, 256, 256, 48, 48, 1, False, "REG"), (2, 128, 128, 128, 128, 3, False, "DMA"),
+                                    (8, 64, 256, 16, 512, 3, True, "ROW3N"), (8, 128, 128, 128, 256, 3, False, "ROW3N"),
+                                    (16, 64, 384, 64, 64, 3, False, "ROW3N"), (32, 768, 768, 32, 32, 3, False, "ROW3N"),
+                                    (1, 256, 256, 239, 240, 1, False, "PP"), (9, 64, 256, 80, 80, 3, False, "PP")])
 def test_conv_kernels_are_race_free(shape):
     """The forward kernels have no atomics: repeated launches on the same operands must agree bit for bit, and a
     staging race (an LDS-DMA piece still in flight when another wave reads it) shows up as a difference.  Shapes of the
-    row-sharing kernel, the ping-pong kernel and the 128x128 LDS-DMA kernel, at sizes that fill the chip."""
+    row-sharing kernel on both tiles, the ping-pong kernel and the 128x128 kernels; the first launch must carry the clock label of
+    the kernel the shape is listed with."""
     from multi_stylegan_amd import conv_ops
-    b, i, o, h, w_, k, per_sample = shape
+    b, i, o, h, w_, k, per_sample, kernel = shape
     torch.manual_seed(b * 1000 + i)
     x = conv_ops.to_compute_layout(torch.randn(b, i, h, w_, device=DEV), torch.bfloat16)
     w = torch.randn((b, o, i, k, k) if per_sample else (o, i, k, k), device=DEV) / math.sqrt(i * k * k)
     geo = conv_ops.Geometry("conv", k, k, 1, k // 2, (h, w_), per_sample)
-    first = conv_ops._f_raw(x, w, None, geo).clone()
+    first = _clocked(lambda: conv_ops._f_raw(x, w, None, geo), kernel).clone()
     for _ in range(12):
         again = conv_ops._f_raw(x, w, None, geo)
         assert torch.equal(first, again)
@@ -1085,18 +1192,25 @@ def test_image_head_gradient_handed_to_the_producer(batch, monkeypatch):
             assert e < (1e-2 if a.dtype == bf else 2e-2 if name == "noise_w" else 5e-3), (name, second, e)   # (noise_w: one cancelling sum)
 
 
-@pytest.mark.parametrize("case", ["128ch_small_tile", "256ch_large_tile", "sign_from_the_map", "with_residual"])
+@pytest.mark.parametrize("case", ["128ch_small_tile", "256ch_large_tile", "sign_from_the_map", "with_residual", "pp_tile"])
 def test_activation_backward_in_the_data_gradient_epilogue(case, monkeypatch):
     """conv -> bias + leaky ReLU -> conv (the main path of a discriminator block): with the hand-over (conv_ops.ActHandle) the
     second conv's data-gradient launch applies the first activation's backward in its epilogue (msg_conv2d_fprop_act_backward)
     and leaves the bias gradient; the map between the two backward nodes is not written.  Same arithmetic on the same rounded
     values as the two-pass form: input and weight gradients bit for bit, the bias gradient (another summation order) to 1e-5.
     Sign source: the first conv's sign bytes (tiles of 128 / 256 pixels) or, when no bytes were written, its stored output;
-    with_residual: the second conv's input has a second gradient that meets the data gradient in the same epilogue."""
+    with_residual: the second conv's input has a second gradient that meets the data gradient in the same epilogue.
+    pp_tile (9 x 256 channels on 80-wide maps): the second conv's data gradient belongs to the ping-pong kernel, which has no such
+    epilogue -- the plan query answers MSG_PLAN_PP with no partial-sum rows at epilogue 3 and msg_conv2d_fprop_act_backward refuses
+    the problem.  The armed hand-over must then be declined: no `_actbwd` launch, the data gradient under the ping-pong kernel's
+    label, and the producer applies its own activation backward -- the same bits as with the hand-over switched off."""
     from multi_stylegan_amd import _lib, conv_ops
     from multi_stylegan_amd.op_static import fused_act
     bf = torch.bfloat16
-    b, c, hw = (16, 256, 128) if case == "256ch_large_tile" else (4, 128, 128)
+    b, c, hw = {"256ch_large_tile": (16, 256, 128), "pp_tile": (9, 256, 80)}.get(case, (4, 128, 128))
+    if case == "pp_tile":
+        ldy, no_rows = c, 0
+        assert conv_ops._fprop_plan(_lib.MSG_BF16, b, hw, hw, c, c, hw, hw, c, ldy, 3, 3, 1, 1, 1, 0, 0, 0, 3)[::3] == (_lib.MSG_PLAN_PP, no_rows)
 
     def run(fuse):
         monkeypatch.setattr(conv_ops, "ACT_BACKWARD_IN_DGRAD", fuse)
@@ -1126,8 +1240,10 @@ def test_activation_backward_in_the_data_gradient_epilogue(case, monkeypatch):
 
     g1, k1 = run(True)
     g0, k0 = run(False)
-    assert any("_actbwd" in k for k in k1), k1
+    assert any("_actbwd" in k for k in k1) == (case != "pp_tile"), k1
     assert not any("_actbwd" in k for k in k0)
+    if case == "pp_tile":
+        assert "conv_fprop_pp/bf16" in k1 and "conv_fprop_pp/bf16" in k0, (k1, k0)
     for name, a, r in zip(("x", "w1", "w2", "b1", "b2"), g1, g0):
         if name == "b1":
             assert rel_err(a, r) < 1e-5, name

@@ -1093,3 +1093,48 @@ def test_bench_dump_outputs(tmp_path, monkeypatch):
     sample = np.load(tmp_path / "a" / "generator_params.npy")
     flat = torch.cat([p.detach().reshape(-1) for p in big.parameters()]).numpy()
     assert sample.shape == (50,) and np.isin(sample, flat).all()
+
+
+def test_conv_kernel_case_table_selects_the_kernels_it_names():
+    """tests/conv_kernel_cases.py, the shapes the float64-referenced GPU tests of the large-tile kernels run (test_hip_conv.py::
+    test_large_tile_kernels_against_float64): msg_conv2d_fprop_launch_plan on the launches each case turns into names the kernel the
+    case is for -- the forward launch plain, with a bias, with the fused activation and with the residual merge (the last three for
+    the stride-1 convs, the launches that take them), then the data gradient.  Two shapes one tile below a floor name the 128 x 128
+    kernels: an eligibility rule that moves shows up here, on any machine, not as coverage that quietly went elsewhere.  Then the
+    table as a whole: every large-tile kernel with both weight modes and as a data gradient, and the tails and map widths the
+    kernels branch on."""
+    import conv_kernel_cases as table
+    from multi_stylegan_amd import _lib
+    from multi_stylegan_amd.build import build
+    from tools.gen_dispatch_table import fprop_plan
+    build(verbose=False)
+    lib = _lib.lib()
+    code = lambda kernel: getattr(_lib, "MSG_PLAN_" + kernel)
+    names = [c.name for c in table.CASES + table.GUARD_CASES]
+    assert len(set(names)) == len(names) and set(table.EPILOGUE_CASES) <= set(table.BY_NAME)
+    large = {"PP", "ROW3", "ROW3N"}
+    fwd, dgrad = [], []                      # (case, launch) of the launches that run on a large tile
+    for c in table.CASES + table.GUARD_CASES:
+        f, d = table.launches(c, _lib.MSG_BF16)
+        assert fprop_plan(lib, list(f))[0] == code(c.fwd), (c.name, "forward")
+        if c.kind == "conv" and c.stride == 1:
+            for has_bias, epilogue in ((1, 0), (0, 1), (0, 2)):
+                leg = table.launches(c, _lib.MSG_BF16, has_bias, epilogue)[0]
+                assert fprop_plan(lib, list(leg))[0] == code(c.fwd), (c.name, "forward", has_bias, epilogue)
+        if c.dgrad is None:                  # a guard row
+            assert c.fwd not in large
+            continue
+        assert fprop_plan(lib, list(d))[0] == code(c.dgrad), (c.name, "data gradient")
+        assert c.fwd in large or c.dgrad in large, c.name
+        fwd += [(c, f)] if c.fwd in large else []
+        dgrad += [(c, d)] if c.dgrad in large else []
+    assert {c.fwd for c, _ in fwd if not c.per_sample} == large and {c.fwd for c, _ in fwd if c.per_sample} == large
+    assert {c.dgrad for c, _ in dgrad} == large
+    T = table
+    pp = [(c, a) for c, a in fwd if c.fwd == "PP"] + [(c, a) for c, a in dgrad if c.dgrad == "PP"]
+    assert any(a[T.PIXEL_SHUFFLE] for c, a in fwd if c.fwd == "PP") and any(a[T.PIXEL_SHUFFLE] for c, a in dgrad if c.dgrad == "PP")
+    assert any(table.gemm_rows(a) % 256 for _, a in pp), "ragged last M tile"
+    assert any(a[T.N_] % 256 for _, a in pp), "N tail"
+    assert any(a[T.CX] < a[T.CK] for _, a in pp), "Cx < Ck"
+    row_sharing = [a for c, a in fwd if c.fwd != "PP"] + [a for c, a in dgrad if c.dgrad != "PP"]
+    assert {32, 64, 128, 256, 512} <= {a[T.OW] for a in row_sharing}
