@@ -509,7 +509,8 @@ int msg_linear_wgrad(const float* gy, const float* x, float* gw, float* gb, int 
  * ModulatedConv2d's modulation_mapping applied to its slot of the latent [M][L][K], all known before the first conv):
  * group g reads rows x + slot[g]*K (row pitch L*K), its own weight w[g] ([N][K]) / bias[g] (device pointer tables;
  * `bias` itself may be NULL), and writes the g-th slab of the [G][M][N] (fprop), [G][M][K] (dgrad), [G][N][K] / [G][N]
- * (wgrad) outputs.  Same arithmetic per group as msg_linear_fprop / _dgrad / _wgrad. */
+ * (wgrad) outputs.  Same arithmetic per group as msg_linear_fprop / _dgrad / _wgrad.  M == 0: fprop and dgrad are no-ops; both
+ * wgrad entries, like msg_linear_wgrad, still write their (zero) gradients, and gy and x may then be NULL.  G == 0: no-op. */
 int msg_linear_grouped_fprop(const float* x, const int* slot, const float* const* w, const float* const* bias, float* y,
                              int G, int M, int N, int K, int L, float gain, float bias_gain, void* stream);
 int msg_linear_grouped_dgrad(const float* gy, const float* const* w, float* gx, int G, int M, int N, int K, float gain,

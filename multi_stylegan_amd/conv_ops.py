@@ -1329,10 +1329,12 @@ class _LinF(Function):
     @staticmethod
     def forward(ctx, x, w, bias, gain, bias_gain=1.0):
         _lib.require_gpu(x, w, bias)
-        x, w, bias = _dense32(x, w, bias)
-        (m, k), n = x.shape, w.shape[0]
+        xd, wd, bias = _dense32(x, w, bias)
+        (m, k), n = xd.shape, wd.shape[0]
         y = torch.empty((m, n), dtype=torch.float32, device=x.device)
-        _lin_call("linear_fprop", 2.0 * m * n * k, x, w, bias, y, m, n, k, float(gain), float(bias_gain))
+        _lin_call("linear_fprop", 2.0 * m * n * k, xd, wd, bias, y, m, n, k, float(gain), float(bias_gain))
+        # the arguments themselves, not their dense copies: a copy made in here has no history, and a higher-order graph
+        # through it would silently lose the derivative in a non-contiguous x or w (a latent slice, a transposed view)
         ctx.save_for_backward(x, w)
         ctx.gain, ctx.has_bias, ctx.bias_gain = float(gain), bias is not None, float(bias_gain)
         ctx.bias_param = bias
@@ -1345,7 +1347,7 @@ class _LinF(Function):
         gx = _derive(_LinD, gy, w, ctx.gain) if need_x else None
         gw = gb = None
         if need_w and need_b and ctx.has_bias and not torch.is_grad_enabled():
-            (gy_,) = _dense32(gy)                     # first-order step: weight and bias gradient in one launch
+            gy_, x = _dense32(gy, x)                  # first-order step: weight and bias gradient in one launch
             (m, n), k = gy_.shape, x.shape[1]
             gw, gb = _grad_dest(w), _grad_dest(ctx.bias_param)        # (their slices of the flat gradient store, if free)
             gw = gw if gw is not None else torch.empty((n, k), dtype=torch.float32, device=x.device)
@@ -1365,11 +1367,11 @@ class _LinD(Function):
     @staticmethod
     def forward(ctx, gy, w, gain):
         _lib.require_gpu(gy, w)
+        ctx.save_for_backward(gy, w)                  # (as given: see _LinF.forward)
         gy, w = _dense32(gy, w)
         (m, n), k = gy.shape, w.shape[1]
         gx = torch.empty((m, k), dtype=torch.float32, device=gy.device)
         _lin_call("linear_dgrad", 2.0 * m * n * k, gy, w, gx, m, n, k, float(gain))
-        ctx.save_for_backward(gy, w)
         ctx.gain = float(gain)
         return gx
 
@@ -1387,11 +1389,11 @@ class _LinG(Function):
     @staticmethod
     def forward(ctx, gy, x, gain):
         _lib.require_gpu(gy, x)
+        ctx.save_for_backward(gy, x)                  # (as given: see _LinF.forward)
         gy, x = _dense32(gy, x)
         (m, n), k = gy.shape, x.shape[1]
         gw = torch.empty((n, k), dtype=torch.float32, device=gy.device)
         _lin_call("linear_wgrad", 2.0 * m * n * k, gy, x, gw, None, m, n, k, float(gain), 1.0)
-        ctx.save_for_backward(gy, x)
         ctx.gain = float(gain)
         return gw
 

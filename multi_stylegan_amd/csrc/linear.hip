@@ -253,7 +253,9 @@ extern "C" int msg_linear_grouped_dgrad(const float* gy, const float* const* w, 
 extern "C" int msg_linear_grouped_wgrad(const float* gy, const float* x, const int* slot, float* gw, float* gb, int G,
                                         int M, int N, int K, int L, float gain, float bias_gain, void* stream) {
     if (G == 0) return MSG_OK;
-    if (M <= 0 || lin_bad(gy, x, gw, M, N, K) || !slot || G < 0 || L <= 0 || G > 65535) return MSG_EINVAL;
+    // (empty batch: as in msg_linear_wgrad the gradient is zero and must still be written -- the kernel's sums over m are
+    //  empty, so it stores gain * 0 and reads neither gy nor x, which may then be NULL)
+    if (M < 0 || (M > 0 && (!gy || !x)) || !gw || N <= 0 || K <= 0 || !slot || G < 0 || L <= 0 || G > 65535) return MSG_EINVAL;
     hipLaunchKernelGGL(linear_grouped_wgrad_kernel, dim3(N, G), dim3(256), 0, (hipStream_t)stream, gy, x, slot, gw, gb,
                        M, N, K, L, gain, bias_gain);
     return MSG_CHECK_LAUNCH();
@@ -265,7 +267,7 @@ extern "C" int msg_linear_grouped_wgrad_ptrs(const float* gy, const float* x, co
                                              float* const* gb, int G, int M, int N, int K, int L, float gain, float bias_gain,
                                              void* stream) {
     if (G == 0) return MSG_OK;
-    if (M <= 0 || lin_bad(gy, x, gw, M, N, K) || !slot || G < 0 || L <= 0 || G > 65535) return MSG_EINVAL;
+    if (M < 0 || (M > 0 && (!gy || !x)) || !gw || N <= 0 || K <= 0 || !slot || G < 0 || L <= 0 || G > 65535) return MSG_EINVAL;
     hipLaunchKernelGGL(linear_grouped_wgrad_ptrs_kernel, dim3(N, G), dim3(256), 0, (hipStream_t)stream, gy, x, slot, gw, gb,
                        M, N, K, L, gain, bias_gain);
     return MSG_CHECK_LAUNCH();

@@ -22,21 +22,19 @@ Largest errors measured on the MI355X (the case closest to its bound, per entry 
 Every reduction stayed under 0.4 of its bound.  Each case prints its own figures; the fixture prints the largest.
 """
 import functools
-import math
 
 import pytest
 import torch
 
 import modulate_util as mu
+from abi_util import DEV, Guarded, _ptr, _shifted, _stream
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
 F32, BF16 = 0, 1
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16}
 FLOOR = 2.0 ** -21
-SENTINEL = 1536.0                       # exact in bfloat16
 GAIN = 0.37
 EPS = 1e-8
 WORST = {}                              # entry / quantity -> (error, bound, case): printed when the module is done
@@ -57,49 +55,8 @@ def _note(key, err, bound, case):
         WORST[key] = (err, bound, case)
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _dev(t):
     return t.to(DEV, torch.float32).contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _shifted(t):
-    """The same values 4 bytes off a 16-byte boundary -> (tensor that owns the memory, pointer)."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    buf[1:].copy_(t.reshape(-1))
-    return buf, buf.data_ptr() + t.element_size()
-
-
-class Guarded:
-    """An output of `shape`, NaN everywhere (0x7FC0 in bf16), with one more row of `row` sentinel values behind it."""
-
-    def __init__(self, shape, row, dtype=torch.float32):
-        self.shape, self.n = tuple(shape), math.prod(shape)
-        self.buf = torch.full((self.n + row,), float("nan"), dtype=dtype, device=DEV)
-        self.buf[self.n:] = SENTINEL
-        self.ptr = self.buf.data_ptr()
-
-    def _host(self):
-        torch.cuda.synchronize()
-        host = self.buf.cpu()
-        assert bool((host[self.n:] == SENTINEL).all()), "the guard row behind the output was written"
-        return host[:self.n]
-
-    def read(self):
-        """The output in float64 on the host: every element written, the guard untouched."""
-        out = self._host()
-        left = int(torch.isnan(out).sum())
-        assert left == 0, f"{left} of {self.n} output elements were not written"
-        return out.double().reshape(self.shape)
-
-    def assert_untouched(self):
-        assert bool(torch.isnan(self._host()).all()), "a refused call wrote to its output"
 
 
 # ------------------------------------------------------------------------------------------- element-wise images
