@@ -15,7 +15,7 @@ Geometries: "conv" (kh x kw, stride 1 or 2, any padding) and "up2" (the generato
 run as a 1x1 contraction to 4*O channels stored pixel-shuffled).  Weights are given in the reference's parameter
 layout ([O,I,kh,kw], or [B,O,I,kh,kw] for the per-sample weights of the modulated convolution); their K-contiguous
 kernel-side images are built by one kernel per parameter and cached until that parameter's optimizer steps
-(_param_images); activations are channels-last with a 16-byte-aligned channel stride.  Fused forms: conv + activation
+(weight_images.py); activations are channels-last with a 16-byte-aligned channel stride.  Fused forms: conv + activation
 (_ConvActF, _ModulatedConv with fuse_act), conv + residual merge (_ConvResidualF).
 There is no CPU or library fallback.
 """
@@ -28,17 +28,15 @@ from typing import Optional, Tuple
 import torch
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, weight_images
 from ._autograd import _derive
+from .weight_images import _k_run, _oi, _round_up
+from .weight_images import invalidate_weight_cache  # noqa: F401  (public here as well: callers outside the package)
 
 
 # ----------------------------------------------------------------------------------------------- layout helpers
 def _vec(dtype) -> int:
     return 8 if dtype == torch.bfloat16 else 4
-
-
-def _round_up(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
 
 
 def _padded_nhwc(b, c, h, w, dtype, device):
@@ -213,189 +211,13 @@ def _alloc_out(b: int, n: int, h: int, w: int, dtype, device) -> Tuple[torch.Ten
     return buf.permute(0, 3, 1, 2)[:, :n], ld
 
 
-def _relayout_kernel_ok(w, dtype, taps) -> bool:
-    return w.is_cuda and w.dtype == torch.float32 and dtype in (torch.bfloat16, torch.float32) and \
-        taps <= 16 and w.ndim >= 4
-
-
-def _relay_fwd(w: torch.Tensor, dtype) -> Tuple[torch.Tensor, int]:
-    """[..., O, I, kh, kw] -> [..., O, kh*kw, Ck] (K-contiguous, input channels zero-padded to a 128-byte run)."""
-    if w.ndim == 2:
-        w = w[:, :, None, None]
-    *lead, o, i, kh, kw = w.shape
-    ck = _round_up(i, 128 // (2 if dtype == torch.bfloat16 else 4))
-    if _relayout_kernel_ok(w, dtype, kh * kw):
-        # per-sample (or any non-parameter) fp32 weights: the kernel of _param_images, the leading dimensions folded
-        # into the rows -- one pass instead of a zero fill and a transposing, casting copy
-        rows = w.numel() // (i * kh * kw)
-        out = torch.empty((*lead, o, kh * kw, ck), dtype=dtype, device=w.device)
-        with _lib.on_device(w.device):
-            code = _lib.lib().msg_relayout_weight(w.detach().contiguous().data_ptr(), out.data_ptr(), None, None,
-                                                  _lib.dtype_code(out), rows, i, kh * kw, ck, ck, 0, 0, 1.0,
-                                                  _lib.stream_of(w.device))
-        _lib.check(code, "msg_relayout_weight")
-        return out, ck
-    out = torch.zeros((*lead, o, kh * kw, ck), dtype=dtype, device=w.device)
-    out[..., :i] = w.reshape(*lead, o, i, kh * kw).transpose(-1, -2)
-    return out, ck
-
-
-def _relay_dgrad(w: torch.Tensor, dtype, flip: bool) -> Tuple[torch.Tensor, int]:
-    """[..., O, I, kh, kw] -> [..., I, kh*kw (flipped if asked), Ok]: the weights of the data-gradient contraction."""
-    if w.ndim == 2:
-        w = w[:, :, None, None]
-    *lead, o, i, kh, kw = w.shape
-    ok = _round_up(o, 128 // (2 if dtype == torch.bfloat16 else 4))
-    if _relayout_kernel_ok(w, dtype, kh * kw) and len(lead) <= 1:
-        n = lead[0] if lead else 1
-        out = torch.empty((*lead, i, kh * kw, ok), dtype=dtype, device=w.device)
-        w3 = w.detach().contiguous().view(n, o, i, kh * kw)
-        ov = out.view(n, i, kh * kw, ok)
-        with _lib.on_device(w.device):
-            for k in range(n):                      # (the data-gradient image is per sample: one small launch each)
-                code = _lib.lib().msg_relayout_weight(w3[k].data_ptr(), None, ov[k].data_ptr(), None, _lib.dtype_code(out),
-                                                      o, i, kh * kw, ok, ok, int(flip), 0, 1.0, _lib.stream_of(w.device))
-                _lib.check(code, "msg_relayout_weight")
-        return out, ok
-    src = w.reshape(*lead, o, i, kh * kw)
-    if flip:
-        src = src.flip(-1)
-    out = torch.zeros((*lead, i, kh * kw, ok), dtype=dtype, device=w.device)
-    out[..., :o] = src.permute(*range(len(lead)), len(lead) + 1, len(lead) + 2, len(lead))
-    return out, ok
-
-
-def _s2_plan(k: int, pad: int):
-    """Stride-2 data gradient as a stride-1 gather over gy, one sub-filter per output parity (1-D plan).
-    gx[2c + ph] = sum_u gy[c + e - u] * w[t0 + 2u]  with t0 = (ph + pad) % 2, e = (ph + pad - t0) / 2.
-    -> (taps U, pad', table[ph][tau] = forward tap index or -1): gy index = c + tau - pad'."""
-    offs = {}
-    for ph in (0, 1):
-        t0 = (ph + pad) % 2
-        e = (ph + pad - t0) // 2
-        for u in range((k - t0 + 1) // 2):
-            offs[(ph, e - u)] = t0 + 2 * u
-    dmin = min(d for _, d in offs)
-    dmax = max(d for _, d in offs)
-    taps = dmax - dmin + 1
-    table = [[offs.get((ph, tau + dmin), -1) for tau in range(taps)] for ph in (0, 1)]
-    return taps, -dmin, table
-
-
-def _relay_dgrad_s2(w: torch.Tensor, dtype, pad: int) -> Tuple[torch.Tensor, int, int, int]:
-    """[..., O, I, k, k] -> [..., 4*I, U*U, Ok]: the stride-2 data gradient as ONE stride-1 conv over gy with U x U taps
-    whose 4*I output channels are the four output parities (written pixel-shuffled by the kernel).  Compared with
-    the zero-insertion form (in_up = 2) the matrix cores skip the 3/4 of the taps that only ever meet parity holes."""
-    *lead, o, i, kh, kw = w.shape
-    assert kh == kw
-    taps, pad2, table = _s2_plan(kh, pad)
-    ok = _round_up(o, 128 // (2 if dtype == torch.bfloat16 else 4))
-    # one gather instead of a copy per (parity, tap): source tap index per (parity, tap), kh * kw = "no tap" (a zero plane)
-    src = [[(table[ph][th] * kw + table[pw][tw]) if table[ph][th] >= 0 and table[pw][tw] >= 0 else kh * kw
-            for th in range(taps) for tw in range(taps)] for ph in (0, 1) for pw in (0, 1)]
-    idx = torch.tensor(src, dtype=torch.long, device=w.device)                   # [4, taps^2]
-    wt = w.transpose(-4, -3).reshape(*lead, i, o, kh * kw)                       # [..., I, O, kh*kw]
-    wz = torch.cat([wt, wt.new_zeros((*lead, i, o, 1))], dim=-1)                 # (+ the zero plane)
-    picked = wz[..., idx]                                                        # [..., I, O, 4, taps^2]
-    n = len(lead)
-    picked = picked.permute(*range(n), n + 2, n, n + 3, n + 1)                   # [..., 4, I, taps^2, O]
-    out = torch.zeros((*lead, 4, i, taps * taps, ok), dtype=dtype, device=w.device)
-    out[..., :o] = picked
-    return out.reshape(*lead, 4 * i, taps * taps, ok), ok, taps, pad2
-
-
-# Re-laid copies of PARAMETERS are cached between weight updates: D runs three times and G two to three times per
-# iteration on unchanged weights.  The cache lives ON the nn.Parameter object (it dies with it and can never alias a
-# recycled address) and is validated against (a) the tensor's in-place version counter and (b) a global weight
-# generation that every torch optimizer step bumps (fused/foreach optimizers and `.data` writes do not touch the
-# version counter).  Code that writes parameters behind both mechanisms must call invalidate_weight_cache().
-_WEIGHT_GENERATION = [0]
-
-
-def invalidate_weight_cache(params=None) -> None:
-    """Declare parameters changed behind autograd's back (`.data` writes, fused / foreach optimizers do not bump the
-    tensors' version counters): the given ones, or -- with no argument -- every cached image of every parameter."""
-    if params is None:
-        _WEIGHT_GENERATION[0] += 1
-        return
-    for p in params:
-        p.__dict__["_msg_gen"] = p.__dict__.get("_msg_gen", 0) + 1
-
-
-def _after_optimizer_step(optimizer, *_args, **_kwargs) -> None:
-    # only the parameters THIS optimizer owns changed: the discriminator's step must not throw away the generator's
-    # re-laid weights (and vice versa) -- with one global generation every weight was re-laid twice per iteration
-    for group in optimizer.param_groups:
-        invalidate_weight_cache(group["params"])
-
-
-def _stamp(w):
-    return (w._version, _WEIGHT_GENERATION[0], w.__dict__.get("_msg_gen", 0), w.data_ptr())
-
-
-from torch.optim.optimizer import register_optimizer_step_post_hook as _register_step_hook  # noqa: E402
-
-_register_step_hook(_after_optimizer_step)
-
-
-def _cached(w, tag, dtype, wscale, build):
-    if not isinstance(w, torch.nn.Parameter):
-        out = build()
-        return (out[0] * wscale, *out[1:]) if wscale != 1.0 else out
-    store = w.__dict__.setdefault("_msg_relay", {})
-    key = (tag, dtype, wscale)
-    stamp = _stamp(w)
-    hit = store.get(key)
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
-    with torch.no_grad():
-        out = build()
-        if wscale != 1.0:
-            out = (out[0] * wscale, *out[1:])
-    store[key] = (stamp, out)
-    return out
-
-
-def _param_images(w, dtype, gain, kind, modulation=False):
-    """{'f': (fwd image, ck), 'd': (dgrad image, ok)[, 'wsq': sum_t w^2]} of a shared-weight PARAMETER, built by ONE
-    kernel (csrc/relayout.hip) per weight update and cached on the parameter.  `modulation`: the fp32, unpadded base
-    images + wsq that the modulated conv scales per sample.  Returns None when the fast path does not apply (then the
-    torch re-layout functions are used)."""
-    key = ("img", dtype, gain, kind, modulation)
-    store = w.__dict__.get("_msg_relay")
-    if store is not None:                      # (the hit path first: ~240 lookups per training iteration on the host's critical path)
-        hit = store.get(key)
-        if hit is not None and hit[0] == (w._version, _WEIGHT_GENERATION[0], w.__dict__.get("_msg_gen", 0), w.data_ptr()):
-            return hit[1]
-    if not (isinstance(w, torch.nn.Parameter) and w.is_cuda and w.dtype == torch.float32):
-        return None
-    o, i = _oi(w)
-    t = w.numel() // (o * i)
-    if t > 16 or w.numel() != o * i * t:
-        return None
-    store = w.__dict__.setdefault("_msg_relay", {})
-    stamp = _stamp(w)
-    dev = w.device
-    unit = 1 if modulation else 128 // (2 if dtype == torch.bfloat16 else 4)
-    ck, ok = _round_up(i, unit), _round_up(o, unit)
-    up2 = kind == "up2"
-    with torch.no_grad():
-        w3 = w.detach().reshape(o, i, t).contiguous()
-        fwd = torch.empty((t * o, 1, ck) if up2 else (o, t, ck), dtype=dtype, device=dev)
-        dgr = torch.empty((i, t, ok), dtype=dtype, device=dev)
-        wsq = torch.empty((o, i), dtype=torch.float32, device=dev) if modulation else None
-        with _lib.on_device(dev):
-            code = _lib.lib().msg_relayout_weight(w3.data_ptr(), fwd.data_ptr(), dgr.data_ptr(), _lib.ptr(wsq),
-                                                  _lib.dtype_code(fwd), o, i, t, ck, ok, int(not up2), int(up2),
-                                                  float(gain), _lib.stream_of(dev))
-        _lib.check(code, "msg_relayout_weight")
-    out = {"f": (fwd, ck), "d": (dgr, ok), "wsq": wsq}
-    store[key] = (stamp, out)
-    return out
-
-
 # --------------------------------------------------------------------------------------------------- raw launches
 _CLOCK_SHAPES = bool(int(os.environ.get("MSG_CLOCK_SHAPES", "0")))   # per-shape timing keys (tools/shape_table.py)
+
+
+def _shape_key(b, in_hw, out_hw, c_in, c_out, kh, kw, stride, tail="") -> str:
+    """The per-shape part of a kernel-clock label."""
+    return f"|B{b} {in_hw[0]}x{in_hw[1]}->{out_hw[0]}x{out_hw[1]} {c_in}->{c_out} {kh}x{kw} s{stride}{tail}|"
 
 # How the contractions of the fp32-STORAGE path multiply (conv forward / data gradient / weight gradient; include/msg_hip.h):
 #   "exact"        -- v_mfma_f32_32x32x2_f32, bit-for-bit an fp32 fma chain (the default: what the 1e-3 parity gate was built on);
@@ -511,8 +333,8 @@ def _launch_fprop(x, wk, ck, bias, n, out_hw, kh, kw, stride, pad, in_up, pixel_
                                               int(pixel_shuffle), wstride, int(bias is not None),
                                               2 if residual is not None else int(act is not None))
     if _lib.kernel_clock.enabled and _CLOCK_SHAPES:     # (key: the timing's label -- the kernel the library will pick)
-        key += f"|B{b} {ih}x{iw}->{oh}x{ow} {c_real}->{n} {kh}x{kw} s{stride} up{in_up}" \
-               f"{' ps' if pixel_shuffle else ''}{' per-sample' if per_sample else ''}|"
+        key += _shape_key(b, (ih, iw), out_hw, c_real, n, kh, kw, stride,
+                          f" up{in_up}{' ps' if pixel_shuffle else ''}{' per-sample' if per_sample else ''}")
     with _lib.on_device(dev), _lib.kernel_clock.span((key, 'bf16' if x.dtype == torch.bfloat16 else 'f32'), flops):
         if residual is not None:
             assert bias is None and act is None and in_up == 1 and not pixel_shuffle
@@ -582,8 +404,8 @@ def _launch_wgrad(gy, x, o, i, kh, kw, stride, pad, pixel_shuffle, per_sample, l
     flops = 2.0 * b * oh * ow * o * i * taps
     key = "conv_wgrad"
     if _CLOCK_SHAPES and _lib.kernel_clock.enabled:
-        key += f"|B{b} {ih}x{iw}->{oh}x{ow} {i}->{o} {kh}x{kw} s{stride}{' ps' if pixel_shuffle else ''}" \
-               f"{' per-sample' if per_sample else ' shared'}{f' slabs{nz}' if need else ''}|"
+        key += _shape_key(b, (ih, iw), (oh, ow), i, o, kh, kw, stride, f"{' ps' if pixel_shuffle else ''}"
+                          f"{' per-sample' if per_sample else ' shared'}{f' slabs{nz}' if need else ''}")
     with _lib.on_device(dev), _lib.kernel_clock.span((key, 'bf16' if x.dtype == torch.bfloat16 else 'f32'), flops):
         code = _lib.lib().msg_conv2d_wgrad(
             gv.data_ptr(), xv.data_ptr(), gw.data_ptr(), *geom, _lib.MSG_WGRAD_K_AUTO, int(oi_major), float(gain), ws, need,
@@ -614,25 +436,12 @@ class Geometry:
             self.y_hw = ((x_hw[0] + 2 * pad - kh) // stride + 1, (x_hw[1] + 2 * pad - kw) // stride + 1)
 
 
-def _oi(w):
-    """(out channels, in channels) of a weight in [O,I], [O,I,kh,kw] or [B,O,I,kh,kw] form."""
-    return (w.shape[0], w.shape[1]) if w.ndim == 2 else (w.shape[-4], w.shape[-3])
-
-
-def _relay_fwd_kind(w, dtype, kind):
-    wk, ck = _relay_fwd(w, dtype)
-    if kind == "up2":                                      # rows n = (2dy+dx)*O + o  <-  w[o, :, dy, dx]
-        o = _oi(w)[0]
-        wk = wk.transpose(-3, -2).reshape(*wk.shape[:-3], 4 * o, 1, ck).contiguous()
-    return wk, ck
-
-
 def _thin_ok(dtype, i, g: Geometry) -> bool:
     """A 'same' kh x kw conv whose (tap, channel) pairs fit ONE 128-byte K run (the discriminator's 6-channel first layer):
     it runs as a 1x1 conv over the tap-gathered input (msg_gather_taps)."""
     taps = g.kh * g.kw
     return g.kind == "conv" and g.stride == 1 and not g.per_sample and taps > 1 and \
-        2 * g.pad + 1 == g.kh and g.kh == g.kw and i * taps <= 128 // (2 if dtype == torch.bfloat16 else 4)
+        2 * g.pad + 1 == g.kh and g.kh == g.kw and i * taps <= _k_run(dtype)
 
 
 def _gather_taps(x, i, g: Geometry):
@@ -648,38 +457,36 @@ def _gather_taps(x, i, g: Geometry):
     return out.permute(0, 3, 1, 2), ko
 
 
-def _relay_thin(w, dtype):
-    """[O, I, kh, kw] -> [O, 1, Ko] with K index (tap * I + channel), zero-padded to one 128-byte run."""
-    o, i, kh, kw = w.shape
-    ko = 128 // (2 if dtype == torch.bfloat16 else 4)
-    out = torch.zeros((o, 1, ko), dtype=dtype, device=w.device)
-    out[:, 0, :kh * kw * i] = w.permute(0, 2, 3, 1).reshape(o, kh * kw * i)
-    return out, ko
+def _f_image(x, wk, ck, o, i, g: Geometry, bias=None, act=None, residual=None, out=None):
+    """F with the forward image (wk, ck) of an [O, I] weight in hand -- shared, or one per sample (g.per_sample).  With
+    _d_image the only place that turns a Geometry into launch arguments."""
+    if g.kind == "up2":
+        assert out is None
+        y = _launch_fprop(x, wk, ck, None, 4 * o, g.x_hw, 1, 1, 1, 0, 1, True, g.per_sample, i, mode=g.mode)
+        if residual is None:
+            return y
+        assert residual[1] == 1.0
+        return y + residual[0]                 # (the pixel-shuffling kernel has no residual epilogue)
+    return _launch_fprop(x, wk, ck, bias, o, g.y_hw, g.kh, g.kw, g.stride, g.pad, 1, False, g.per_sample, i,
+                         act=act, residual=residual, out=out, mode=g.mode)
 
 
 def _f_raw(x, w, bias, g: Geometry, act=None, residual=None, out=None):
-    if w.ndim == 4 and _thin_ok(x.dtype, w.shape[1], g):
-        xc, ko = _gather_taps(x, w.shape[1], g)
-        wk, _ = _cached(w, "thin", x.dtype, g.wscale, lambda: _relay_thin(w, x.dtype))
-        return _launch_fprop(xc, wk, ko, bias, w.shape[0], g.y_hw, 1, 1, 1, 0, 1, False, False,
-                             w.shape[1] * g.kh * g.kw, act=act, residual=residual, out=out, mode=g.mode)
-    if g.kind == "up2" and _oi(w)[0] % _vec(x.dtype):
+    o, i = _oi(w)
+    if w.ndim == 4 and _thin_ok(x.dtype, i, g):
+        xc, ko = _gather_taps(x, i, g)
+        wk, _ = weight_images.thin(w, x.dtype, g.wscale)
+        return _launch_fprop(xc, wk, ko, bias, o, g.y_hw, 1, 1, 1, 0, 1, False, False,
+                             i * g.kh * g.kw, act=act, residual=residual, out=out, mode=g.mode)
+    if g.kind == "up2" and o % _vec(x.dtype):
         # the pixel-shuffling epilogue stores whole 16-byte channel vectors per output pixel: pad the output channels
         # with zero filters and drop them again (rare: every up-conv of the models has 512 output channels)
-        o_real = _oi(w)[0]
-        wp = torch.zeros((*w.shape[:-4], _round_up(o_real, _vec(x.dtype)), *w.shape[-3:]), dtype=w.dtype, device=w.device)
-        wp[..., :o_real, :, :, :] = w.detach()
-        assert out is None
-        return _f_raw(x, wp, bias, g, act=act, residual=residual)[:, :o_real]
-    img = _param_images(w, x.dtype, g.wscale, g.kind) if not g.per_sample else None
-    wk, ck = img["f"] if img is not None else \
-        _cached(w, "f" + g.kind, x.dtype, g.wscale, lambda: _relay_fwd_kind(w, x.dtype, g.kind))
-    o, _ = _oi(w)
-    if g.kind == "up2":
-        assert out is None
-        return _launch_fprop(x, wk, ck, None, 4 * o, g.x_hw, 1, 1, 1, 0, 1, True, g.per_sample, _oi(w)[1], mode=g.mode)
-    return _launch_fprop(x, wk, ck, bias, o, g.y_hw, g.kh, g.kw, g.stride, g.pad, 1, False, g.per_sample, _oi(w)[1],
-                         act=act, residual=residual, out=out, mode=g.mode)
+        wp = torch.zeros((*w.shape[:-4], _round_up(o, _vec(x.dtype)), *w.shape[-3:]), dtype=w.dtype, device=w.device)
+        wp[..., :o, :, :, :] = w.detach()
+        assert out is None and residual is None
+        return _f_raw(x, wp, bias, g, act=act)[:, :o]
+    wk, ck = weight_images.forward(w, x.dtype, g.wscale, g.kind, per_sample=g.per_sample)
+    return _f_image(x, wk, ck, o, i, g, bias, act, residual, out)
 
 
 def _act_operands(bias, noise, noise_w, y_shape):
@@ -782,7 +589,7 @@ def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle
     flops = 2.0 * b * h * w_ * n * kh * kw * c_real
     key = label + "_actbwd"                             # (the 256 x 256 tile -- the benchmark's roofline kernel -- or the 128 x 128 one)
     if _lib.kernel_clock.enabled and _CLOCK_SHAPES:
-        key += f"|B{b} {h}x{w_}->{h}x{w_} {c_real}->{n} 3x3 s1 up1{' per-sample' if per_sample else ''}|"
+        key += _shape_key(b, (h, w_), (h, w_), c_real, n, 3, 3, 1, f" up1{' per-sample' if per_sample else ''}")
     with _lib.on_device(dev), _lib.kernel_clock.span((key, 'bf16'), flops):
         code = _lib.lib().msg_conv2d_fprop_act_backward(
             xv.data_ptr(), wk.data_ptr(), y.data_ptr(), _lib.MSG_BF16, b, h, w_, cx, ck, h, w_, n, ldy, kh, kw, 1, 1, wstride,
@@ -793,50 +600,36 @@ def _launch_dgrad_act_backward(gy, wk, ck, n, kh, kw, per_sample, c_real, handle
     return y
 
 
-def _d_raw(gy, w, g: Geometry, residual=None, act_bwd: Optional["ActHandle"] = None, sign_map=None):
-    """act_bwd: the ActHandle of the layer that produced the conv's input, sign_map: that input (= the layer's stored output)."""
-    if act_bwd is not None and act_bwd.armed and not g.per_sample and g.kind == "conv" and g.stride == 1 and g.kh == 3 and \
-            g.kw == 3 and g.pad == 1 and w.ndim == 4:
-        i = _oi(w)[1]
-        img = _param_images(w, gy.dtype, g.wscale, g.kind)
-        wk, ok = img["d"] if img is not None else \
-            _cached(w, "d" + g.kind, gy.dtype, g.wscale, lambda: _relay_dgrad(w, gy.dtype, flip=True))
-        out = _launch_dgrad_act_backward(gy, wk, ok, i, 3, 3, False, _oi(w)[0], act_bwd, residual=residual, mode=g.mode,
+def _d_image(gy, wd, ok, o, i, g: Geometry, residual=None, act_bwd: Optional["ActHandle"] = None, sign_map=None):
+    """D with the data-gradient image (wd, ok) of an [O, I] weight in hand -- shared, or one per sample (g.per_sample).
+    residual = (map shaped like the result, gain): (dgrad + map) * gain in the epilogue (plain stride-1 convs only -- the caller
+    checks).  act_bwd: the armed ActHandle of the layer that produced the conv's input, sign_map: that input (= the layer's
+    stored output) -- a 3x3 'same' conv then tries the launch that applies that layer's activation backward in its epilogue."""
+    if act_bwd is not None and act_bwd.armed and g.kind == "conv" and g.stride == 1 and g.kh == 3 and g.kw == 3 and g.pad == 1:
+        out = _launch_dgrad_act_backward(gy, wd, ok, i, 3, 3, g.per_sample, o, act_bwd, residual=residual, mode=g.mode,
                                          sign_map=sign_map)
         if out is not None:
             return out
-    return _d_raw_plain(gy, w, g, residual)
-
-
-def _d_raw_plain(gy, w, g: Geometry, residual=None):
-    """Data gradient; residual = (map shaped like the result, gain): (dgrad + map) * gain in the epilogue (plain
-    stride-1 convs only -- the caller checks)."""
-    assert residual is None or (g.kind == "conv" and g.stride == 1)
-    if g.kind == "conv" and g.stride == 2 and _oi(w)[1] % _vec(gy.dtype) == 0:
-        return _d_raw_s2(gy, w, g)          # (the pixel-shuffling epilogue needs whole 16-byte channel vectors)
-    i = _oi(w)[1]
-    if w.ndim == 4 and _thin_ok(gy.dtype, i, g) and i <= 8 and gy.shape[1] >= 64:
-        return _d_raw_thin(gy, w, g, residual)
-    img = _param_images(w, gy.dtype, g.wscale, g.kind) if not g.per_sample else None
-    wk, ok = img["d"] if img is not None else \
-        _cached(w, "d" + g.kind, gy.dtype, g.wscale, lambda: _relay_dgrad(w, gy.dtype, flip=g.kind != "up2"))
     if g.kind == "up2":
-        return _launch_fprop(gy, wk, ok, None, i, g.x_hw, 2, 2, 2, 0, 1, False, g.per_sample, _oi(w)[0], mode=g.mode)
-    pad = g.kh - 1 - g.pad
+        return _launch_fprop(gy, wd, ok, None, i, g.x_hw, 2, 2, 2, 0, 1, False, g.per_sample, o, mode=g.mode)
     assert g.kh == g.kw
-    return _launch_fprop(gy, wk, ok, None, i, g.x_hw, g.kh, g.kw, 1, pad, g.stride, False, g.per_sample, _oi(w)[0],
+    return _launch_fprop(gy, wd, ok, None, i, g.x_hw, g.kh, g.kw, 1, g.kh - 1 - g.pad, g.stride, False, g.per_sample, o,
                          residual=residual, mode=g.mode)
 
 
-def _relay_thin_dgrad(w, dtype):
-    """[O, I, kh, kw] -> [Ko, 1, Ok]: row k = tap * I + c holds w[:, c, tap] -- the weights of the 1x1 contraction from the
-    output gradient to the tap-gathered input's gradient (the transpose of _relay_thin)."""
-    o, i, kh, kw = w.shape
-    esz = 2 if dtype == torch.bfloat16 else 4
-    ko, ok = 128 // esz, _round_up(o, 128 // esz)
-    out = torch.zeros((ko, 1, ok), dtype=dtype, device=w.device)
-    out[:kh * kw * i, 0, :o] = w.permute(2, 3, 1, 0).reshape(kh * kw * i, o)
-    return out, ok
+def _d_raw(gy, w, g: Geometry, residual=None, act_bwd: Optional["ActHandle"] = None, sign_map=None):
+    """Data gradient: the route (stride-2 parities / thin / plain), its weight image, the launch.  residual, act_bwd, sign_map:
+    see _d_image.  (The two special routes come first although they have no activation-backward launch: neither can be a
+    problem that launch takes -- it needs stride 1, bf16 and a result whose channels fill whole 16-byte vectors, and a thin 3x3
+    conv has at most 7 input channels in bf16.)"""
+    assert residual is None or (g.kind == "conv" and g.stride == 1)
+    o, i = _oi(w)
+    if g.kind == "conv" and g.stride == 2 and i % _vec(gy.dtype) == 0:
+        return _d_raw_s2(gy, w, g)          # (the pixel-shuffling epilogue needs whole 16-byte channel vectors)
+    if w.ndim == 4 and _thin_ok(gy.dtype, i, g) and i <= 8 and gy.shape[1] >= 64:
+        return _d_raw_thin(gy, w, g, residual)
+    wd, ok = weight_images.dgrad(w, gy.dtype, g.wscale, g.kind, per_sample=g.per_sample)
+    return _d_image(gy, wd, ok, o, i, g, residual, act_bwd, sign_map)
 
 
 def _d_raw_thin(gy, w, g: Geometry, residual=None):
@@ -846,7 +639,7 @@ def _d_raw_thin(gy, w, g: Geometry, residual=None):
     16: 392 us, 37 TFLOP/s) by two streaming passes."""
     o, i = w.shape[0], w.shape[1]
     dev = gy.device
-    wd, ok = _cached(w, "dthin", gy.dtype, g.wscale, lambda: _relay_thin_dgrad(w, gy.dtype))
+    wd, ok = weight_images.thin_dgrad(w, gy.dtype, g.wscale)
     ko = 128 // gy.element_size()
     flops = 2.0 * gy.shape[0] * g.x_hw[0] * g.x_hw[1] * o * i * g.kh * g.kw
     gk = _launch_fprop(gy, wd, ok, None, ko, g.x_hw, 1, 1, 1, 0, 1, False, False, o, flops=flops, mode=g.mode)
@@ -866,25 +659,28 @@ def _d_raw_thin(gy, w, g: Geometry, residual=None):
 
 
 def _d_raw_s2(gy, w, g: Geometry):
-    """Data gradient of a stride-2 conv through the parity decomposition (see _relay_dgrad_s2)."""
+    """Data gradient of a stride-2 conv through the parity decomposition (see weight_images._relay_dgrad_s2)."""
     o, i = _oi(w)
-    wk, ok, taps, pad2 = _cached(w, "ds2", gy.dtype, g.wscale, lambda: _relay_dgrad_s2(w, gy.dtype, g.pad))
+    wk, ok, taps, pad2 = weight_images.dgrad_s2(w, gy.dtype, g.wscale, g.pad)
     hc, wc = (g.x_hw[0] + 1) // 2, (g.x_hw[1] + 1) // 2
     flops = 2.0 * gy.shape[0] * gy.shape[2] * gy.shape[3] * o * i * g.kh * g.kw
     gx = _launch_fprop(gy, wk, ok, None, 4 * i, (hc, wc), taps, taps, 1, pad2, 1, True, g.per_sample, o, flops=flops, mode=g.mode)
     return gx[:, :, :g.x_hw[0], :g.x_hw[1]]
 
 
-def _g_raw(gy, x, o, i, g: Geometry, out=None):
+def _g_raw(gy, x, o, i, g: Geometry, out=None, raw=False):
+    """raw: -> (the gradient in the kernel's layout [(B)][O][taps][ldg], ldg) -- what the modulated conv's fold reads."""
     if _thin_ok(x.dtype, i, g):
+        assert not raw
         # weight gradient of the tap-gathered 1x1 form: gy is read once (not once per tap), one channel tile
         xc, ko = _gather_taps(x, i, g)
         gwp = _launch_wgrad(gy, xc, o, ko, 1, 1, 1, 0, False, False, None, gain=g.wscale, mode=g.mode)      # [O, Ko, 1, 1]
         taps = g.kh * g.kw
         return gwp[:, :taps * i, 0, 0].reshape(o, taps, i).permute(0, 2, 1).reshape(o, i, g.kh, g.kw)
     if g.kind == "up2":
-        return _launch_wgrad(gy, x, o, i, 2, 2, 1, 0, True, g.per_sample, g.x_hw, gain=g.wscale, out=out, mode=g.mode)
-    return _launch_wgrad(gy, x, o, i, g.kh, g.kw, g.stride, g.pad, False, g.per_sample, None, gain=g.wscale, out=out, mode=g.mode)
+        return _launch_wgrad(gy, x, o, i, 2, 2, 1, 0, True, g.per_sample, g.x_hw, raw=raw, gain=g.wscale, out=out, mode=g.mode)
+    return _launch_wgrad(gy, x, o, i, g.kh, g.kw, g.stride, g.pad, False, g.per_sample, None, raw=raw, gain=g.wscale, out=out,
+                         mode=g.mode)
 
 
 def _consumed(ctx, arg_index: int, tensor_ordinal: int) -> bool:
@@ -1653,57 +1449,6 @@ def _scale_rows_cols(base, rowscale, colscale, out, gain):
 _MODCONV_BWD_BATCH = 16
 
 
-def _dgrad_image_base(weight, w3, upsample, kind):
-    """fp32 base of the data-gradient weight image, [I][taps (flipped for convs)][O]."""
-    img = _param_images(weight, torch.float32, 1.0, kind, modulation=True)
-    return img["d"][0] if img is not None else _cached(weight, "md" + kind, torch.float32, 1.0, lambda: (
-        (w3 if upsample else w3.flip(-1)).permute(1, 2, 0).contiguous(), 0))[0]
-
-
-def _fwd_image_base(weight, w3, upsample, kind):
-    """fp32 base of the forward weight image: conv -> [O][taps][I]; up2 -> rows n = q*O + o, one tap."""
-    o, i, t = w3.shape
-    img = _param_images(weight, torch.float32, 1.0, kind, modulation=True)
-    return img["f"][0] if img is not None else _cached(weight, "mb" + kind, torch.float32, 1.0, lambda: (
-        (w3.permute(2, 0, 1).reshape(t * o, 1, i) if upsample else w3.transpose(1, 2)).contiguous(), 0))[0]
-
-
-def _tap_square_sums(weight, w3, kind):
-    """wsq[o][i] = sum over taps of W^2 (cached with the weight)."""
-    img = _param_images(weight, torch.float32, 1.0, kind, modulation=True)
-    return img["wsq"] if img is not None else \
-        _cached(weight, "wsq", torch.float32, 1.0, lambda: (w3.square().sum(dim=2).contiguous(), 0))[0]
-
-
-def _dgrad_modconv(gy, wd, okp, o, i, kh, kw, upsample, g, act_bwd=None, sign_map=None):
-    """Data-gradient contraction of the modulated conv with a per-sample data-gradient weight image; act_bwd: the ActHandle
-    of the layer that produced the conv's input (its activation backward then runs in this launch's epilogue)."""
-    if act_bwd is not None and act_bwd.armed and not upsample and kh == 3 and kw == 3:
-        out = _launch_dgrad_act_backward(gy, wd, okp, i, kh, kw, True, o, act_bwd, mode=g.mode, sign_map=sign_map)
-        if out is not None:
-            return out
-    if upsample:
-        return _launch_fprop(gy, wd, okp, None, i, g.x_hw, 2, 2, 2, 0, 1, False, True, o, mode=g.mode)
-    return _launch_fprop(gy, wd, okp, None, i, g.x_hw, kh, kw, 1, kh - 1 - kh // 2, 1, False, True, o, mode=g.mode)
-
-
-def _fprop_modconv(x, wk, ck, o, i, kh, kw, upsample, g, add_to=None):
-    """Forward contraction of the modulated conv with a per-sample forward weight image; `add_to`: a map shaped like the
-    result that is added to it (in the contraction's epilogue where the kernel has one: the plain stride-1 convs)."""
-    if upsample:
-        y = _launch_fprop(x, wk, ck, None, 4 * o, g.x_hw, 1, 1, 1, 0, 1, True, True, i, mode=g.mode)
-        return y if add_to is None else y + add_to
-    return _launch_fprop(x, wk, ck, None, o, g.y_hw, kh, kw, 1, kh // 2, 1, False, True, i,
-                         residual=None if add_to is None else (add_to, 1.0), mode=g.mode)
-
-
-def _wgrad_modconv(gy, x, o, i, kh, kw, upsample, g):
-    """Per-sample weight gradient in the kernel layout [B][O][taps][ldg] -> (gwk, ldg)."""
-    if upsample:
-        return _launch_wgrad(gy, x, o, i, 2, 2, 1, 0, True, True, g.x_hw, raw=True, mode=g.mode)
-    return _launch_wgrad(gy, x, o, i, kh, kw, 1, kh // 2, False, True, None, raw=True, mode=g.mode)
-
-
 def _fold_weight_gradient(gwk, ldg, w3, s, dd, scale, style_dtype, cotangent=None, dest=None):
     """Per-sample weight gradients -> (dL/dW [1,O,I,kh*kw flat], dL/ds) through msg_modulate_backward; with `cotangent` (v,
     the cotangent of a FIRST backward's style gradient) the second-order terms of msg_modulate_backward2 instead."""
@@ -1741,16 +1486,16 @@ def _modconv_backward(x, weight, style, d, gy, demodulate, upsample, g, scale, n
     w3 = weight.detach().reshape(o, i, t)
     s = style.detach().float().contiguous()
     dd = d if demodulate else None
-    esz = 2 if gy.dtype == torch.bfloat16 else 4
     gx = None
     if need[0]:
-        okp = _round_up(o, 128 // esz)
+        okp = _round_up(o, _k_run(gy.dtype))
         wd = torch.empty((b, i, t, okp), dtype=gy.dtype, device=dev)
-        _scale_rows_cols(_dgrad_image_base(weight, w3, upsample, g.kind), s, dd, wd, scale)
-        gx = _dgrad_modconv(gy, wd, okp, o, i, kh, kw, upsample, g, act_bwd=act_bwd, sign_map=x)
+        base = weight_images.dgrad(weight, torch.float32, 1.0, g.kind, modulation=True)[0]
+        _scale_rows_cols(base, s, dd, wd, scale)
+        gx = _d_image(gy, wd, okp, o, i, g, act_bwd=act_bwd, sign_map=x)
     gw = gs = gwk = None
     if need[1] or need[2]:
-        gwk, ldg = _wgrad_modconv(gy, x, o, i, kh, kw, upsample, g)
+        gwk, ldg = _g_raw(gy, x, o, i, g, raw=True)
         gw3, gs = _fold_weight_gradient(gwk, ldg, w3, s, dd, scale, style.dtype, dest=weight if direct else None)
         gw = gw3.reshape(1, o, i, kh, kw)
     return (gx, gw, gs, gwk) if keep_gwk else (gx, gw, gs)
@@ -1812,22 +1557,18 @@ class _ModConvGrad(Function):
         w3 = weight.detach().reshape(o, i, t)
         s = style.detach().float().contiguous()
         dd = d if demodulate else None
-        esz = 2 if gy.dtype == torch.bfloat16 else 4
-        ck, okp = _round_up(i, 128 // esz), _round_up(o, 128 // esz)
+        ck, okp = _round_up(i, _k_run(gy.dtype)), _round_up(o, _k_run(gy.dtype))
         rows = t * o if upsample else o
         ggy = gx2 = gw3 = gs2 = None
         if a is not None:
             a = a.to(x.dtype)
             if want[0]:                                   # <a, D(gy, w)> is F(a, w) paired with gy
                 wk = torch.empty((b, rows, 1 if upsample else t, ck), dtype=x.dtype, device=dev)
-                base = _fwd_image_base(weight, w3, upsample, g.kind)
-                if demodulate:
-                    _scale_rows_cols(base, d.repeat(1, t) if upsample else d, s, wk, scale)
-                else:
-                    _scale_rows_cols(base, None, s, wk, scale)
-                ggy = _fprop_modconv(a, wk, ck, o, i, kh, kw, upsample, g)
+                base = weight_images.forward(weight, torch.float32, 1.0, g.kind, modulation=True)[0]
+                _scale_rows_cols(base, (d.repeat(1, t) if upsample else d) if demodulate else None, s, wk, scale)
+                ggy = _f_image(a, wk, ck, o, i, g)
             if want[2] or want[3]:                        # ... and G(gy, a) paired with w -> (W, s) through the fold
-                gwk_a, ldg = _wgrad_modconv(gy, a, o, i, kh, kw, upsample, g)
+                gwk_a, ldg = _g_raw(gy, a, o, i, g, raw=True)
                 gw3, gs2 = _fold_weight_gradient(gwk_a, ldg, w3, s, dd, scale, style.dtype)
         if cot_s is not None:
             v = cot_s.detach().float().contiguous()
@@ -1835,10 +1576,10 @@ class _ModConvGrad(Function):
                 # dw = derivative of the weight set along v, in both kernel layouts
                 hf = torch.empty((b, rows, 1 if upsample else t, ck), dtype=x.dtype, device=dev)
                 hd = torch.empty((b, i, t, okp), dtype=gy.dtype, device=dev)
-                base_f = _fwd_image_base(weight, w3, upsample, g.kind)
-                base_d = _dgrad_image_base(weight, w3, upsample, g.kind)
+                base_f = weight_images.forward(weight, torch.float32, 1.0, g.kind, modulation=True)[0]
+                base_d = weight_images.dgrad(weight, torch.float32, 1.0, g.kind, modulation=True)[0]
                 if demodulate:
-                    wsq = _tap_square_sums(weight, w3, g.kind)
+                    wsq = weight_images.tap_square_sums(weight, g.kind)
                     ddir = -(scale * scale) * d.pow(3) * linear(s * v, wsq)          # [B, O]
                     rows_d, rows_dd = (d.repeat(1, t), ddir.repeat(1, t)) if upsample else (d, ddir)
                     with _lib.on_device(dev):
@@ -1855,9 +1596,9 @@ class _ModConvGrad(Function):
                     _scale_rows_cols(base_f, None, v, hf, scale)
                     _scale_rows_cols(base_d, v, None, hd, scale)
                 if want[0]:                               # <dw, G(gy, x)> is F(x, dw) paired with gy ...
-                    ggy = _fprop_modconv(x, hf, ck, o, i, kh, kw, upsample, g, add_to=ggy)
+                    ggy = _f_image(x, hf, ck, o, i, g, residual=None if ggy is None else (ggy, 1.0))
                 if want[1]:                               # ... and D(gy, dw) paired with x
-                    gx2 = _dgrad_modconv(gy, hd, okp, o, i, kh, kw, upsample, g)
+                    gx2 = _d_image(gy, hd, okp, o, i, g)
             if want[2] or want[3]:
                 gw3b, gs2b = _fold_weight_gradient(gwk, gwk.shape[-1], w3, s, dd, scale, style.dtype, cotangent=v)
                 gw3 = gw3b if gw3 is None else gw3 + gw3b
@@ -1889,22 +1630,17 @@ class _ModulatedConv(Function):
         _, o, i, kh, kw = weight.shape
         b, t = x.shape[0], kh * kw
         scale = math.sqrt(2.0) / math.sqrt(i * t)
-        w3 = weight.detach().reshape(o, i, t)
         s = style.detach().float().contiguous()
         d = None
-        esz = 2 if x.dtype == torch.bfloat16 else 4
-        ck = _round_up(i, 128 // esz)
+        ck = _round_up(i, _k_run(x.dtype))
         kind = "up2" if upsample else "conv"
         # base [R][T][C]: conv -> [O][taps][I];  up2 -> rows n = q*O + o, one tap
-        img = _param_images(weight, torch.float32, 1.0, kind, modulation=True)
-        base = img["f"][0] if img is not None else _cached(weight, "mb" + kind, torch.float32, 1.0, lambda: (
-            (w3.permute(2, 0, 1).reshape(t * o, 1, i) if upsample else w3.transpose(1, 2)).contiguous(), 0))[0]
+        base = weight_images.forward(weight, torch.float32, 1.0, kind, modulation=True)[0]
         rows = t * o if upsample else o
         wk = torch.empty((b, rows, 1 if upsample else t, ck), dtype=x.dtype, device=dev)
         if demodulate:
             # demodulation coefficients + weight set in one launch; sum_t W^2 is cached with the weight
-            wsq = img["wsq"] if img is not None else \
-                _cached(weight, "wsq", torch.float32, 1.0, lambda: (w3.square().sum(dim=2).contiguous(), 0))[0]
+            wsq = weight_images.tap_square_sums(weight, kind)
             d = torch.empty((b, o), dtype=torch.float32, device=dev)
             with _lib.on_device(dev):
                 code = _lib.lib().msg_modulate_weights(base.data_ptr(), wsq.data_ptr(), s.data_ptr(), wk.data_ptr(),
@@ -1919,10 +1655,7 @@ class _ModulatedConv(Function):
         if fuse_act:
             assert not upsample, "the upsampling layers blur before their activation"
             act = (*_act_operands(act_bias, noise, noise_w, (b, o, *g.y_hw)), alpha, act_scale, holder)
-        if upsample:
-            y = _launch_fprop(x, wk, ck, None, 4 * o, g.x_hw, 1, 1, 1, 0, 1, True, True, i, mode=g.mode)
-        else:
-            y = _launch_fprop(x, wk, ck, None, o, g.y_hw, kh, kw, 1, kh // 2, 1, False, True, i, act=act, mode=g.mode)
+        y = _f_image(x, wk, ck, o, i, g, act=act)
         ctx.save_for_backward(x, weight, style, d if d is not None else torch.empty(0, device=dev),
                               y if fuse_act else None, noise if fuse_act else None)
         ctx.cfg = (demodulate, upsample, g, scale)

@@ -12,7 +12,7 @@ from typing import Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from . import conv_ops, misc
+from . import misc, weight_images
 
 
 def load_generator_ema(generator: nn.Module, checkpoint: Union[str, Dict]) -> nn.Module:
@@ -23,7 +23,7 @@ def load_generator_ema(generator: nn.Module, checkpoint: Union[str, Dict]) -> nn
     state = checkpoint["generator_ema"] if "generator_ema" in checkpoint else checkpoint
     state = {".".join(part for part in key.split(".") if part != "module"): value for key, value in state.items()}
     generator.load_state_dict(state)
-    conv_ops.invalidate_weight_cache()
+    weight_images.invalidate_weight_cache()
     return generator.eval().requires_grad_(False)
 
 
@@ -61,7 +61,7 @@ class GeneratorSampler:
         """What the captured graph depends on besides its static buffers: the kernel-side weight images are built during the
         warm-up, OUTSIDE the graph, and the graph holds pointers to them.  Any weight change (an EMA step on the wrapped
         generator, load_generator_ema, load_checkpoint, an in-place edit) changes these stamps."""
-        return tuple(conv_ops._stamp(p) for p in self.generator.parameters())
+        return tuple(weight_images._stamp(p) for p in self.generator.parameters())
 
     def reset(self) -> None:
         """Drop the captured graph; the next call re-captures (and re-lays the weights)."""

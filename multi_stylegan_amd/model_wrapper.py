@@ -468,7 +468,7 @@ class ModelWrapper(object):
         ``module.`` prefix of DataParallel checkpoints and the ``discriminator.`` prefix of an ADA-wrapped reference
         discriminator are stripped (or added, when this wrapper's discriminator is itself ADA-wrapped); a reference
         checkpoint's empty ``path_length_regularization`` entry leaves the running mean at its current value."""
-        from . import conv_ops
+        from . import weight_images
         if isinstance(checkpoint, str):
             checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=False)
         self.generator.load_state_dict(_match_keys(checkpoint["generator"], self.generator))
@@ -489,7 +489,7 @@ class ModelWrapper(object):
         if "ada" in extra and callable(getattr(self.discriminator, "load_ada_state", None)):
             self.discriminator.load_ada_state(extra["ada"])
         # load_state_dict copies into the parameters in place: kernel-side weight images cached so far are stale
-        conv_ops.invalidate_weight_cache()
+        weight_images.invalidate_weight_cache()
         # gradients live in the reducers' flat buckets; loading must not have detached them
         self.generator_reducer.zero_grad()
         self.discriminator_reducer.zero_grad()

@@ -166,7 +166,7 @@ class FlatAdam:
         """One Adam update of every bucket; ``coef`` (device scalar, fp32) multiplies the gradients first.  Returns False
         -- nothing done -- if a bucket mixes parameter groups whose hyper-parameters differ (the caller then steps
         through torch)."""
-        from . import conv_ops
+        from . import weight_images
         self._refresh_groups()
         hypers = [self._bucket_hyper(b) for b in self.reducer.buckets]
         if any(h is None for h in hypers):
@@ -189,7 +189,7 @@ class FlatAdam:
                                                     _lib.ptr(coef), lr, b1, b2, eps, self.step_count, 0.0, stream)
                 _lib.check(code, "msg_flat_adam")
         # the parameters changed behind autograd's back: cached kernel-side weight images are stale
-        conv_ops.invalidate_weight_cache([p for b in self.reducer.buckets for p in b.params])
+        weight_images.invalidate_weight_cache([p for b in self.reducer.buckets for p in b.params])
         return True
 
     # ---------------------------------------------------------------------------------------------------------
@@ -230,7 +230,7 @@ class FlatAdam:
 
     def ema_update(self, decay: float = 0.999) -> None:
         """ema <- decay * ema + (1 - decay) * parameter (misc.exponential_moving_average) on the flat stores."""
-        from . import conv_ops
+        from . import weight_images
         if self._ema_model is None:
             raise RuntimeError("FlatAdam.ema_update: attach_ema first")
         if not self._layout_intact() or not self._ema_intact():
@@ -251,4 +251,4 @@ class FlatAdam:
                 ema = [e.data for e, _ in self._ema_rest]
                 torch._foreach_mul_(ema, decay)
                 torch._foreach_add_(ema, [p.data for _, p in self._ema_rest], alpha=1 - decay)
-        conv_ops.invalidate_weight_cache(list(self._ema_model.parameters()))
+        weight_images.invalidate_weight_cache(list(self._ema_model.parameters()))

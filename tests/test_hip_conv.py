@@ -426,32 +426,45 @@ def test_modulated_conv_with_fused_activation_is_bit_identical(noise_batch, dtyp
                          ids=["small", "multi_tile", "1x1", "2x2", "to_rgb", "from_rgb"])
 def test_fused_weight_relayout_matches_torch_relayout(shape, dtype):
     """csrc/relayout.hip (one kernel: forward image, data-gradient image, sum of squared taps) against the torch
-    transpose-copy functions it replaces, bit for bit, for the plain and the transposed-conv (up2) layouts."""
-    from multi_stylegan_amd import conv_ops
+    transpose-copy builders it replaces (weight_images._torch_fwd / _torch_dgrad, called directly), bit for bit, for the plain
+    and the transposed-conv (up2) layouts."""
+    from multi_stylegan_amd import weight_images as wi
     o, i, k = shape
     torch.manual_seed(o + i)
     w = torch.nn.Parameter(torch.randn(o, i, k, k, device=DEV))
     for kind in (("conv", "up2") if k == 2 else ("conv",)):
-        img = conv_ops._param_images(w, dtype, 0.37, kind)
-        assert img is not None
-        f_ref, ck = conv_ops._relay_fwd_kind(w.detach(), dtype, kind)
-        d_ref, ok = conv_ops._relay_dgrad(w.detach(), dtype, flip=kind != "up2")
+        assert wi._fused_images(w, dtype, 0.37, kind, False) is not None           # (the store sends this weight to the kernel)
+        (f_img, f_ck), (d_img, d_ok) = wi.forward(w, dtype, 0.37, kind), wi.dgrad(w, dtype, 0.37, kind)
+        f_ref, ck = wi._torch_fwd(w.detach(), dtype, kind)
+        d_ref, ok = wi._torch_dgrad(w.detach(), dtype, flip=kind != "up2")
         # reference path scales AFTER rounding to the storage type; the fused kernel scales in fp32 and rounds once
         tol = 0 if dtype == torch.float32 else 1e-2
-        assert img["f"][1] == ck and img["d"][1] == ok
-        assert img["f"][0].shape == f_ref.shape and img["d"][0].shape == d_ref.shape
-        assert rel_err(img["f"][0].float(), (f_ref.float() * 0.37)) <= tol + 1e-7
-        assert rel_err(img["d"][0].float(), (d_ref.float() * 0.37)) <= tol + 1e-7
-        assert (img["f"][0][..., i:] == 0).all() and (img["d"][0][..., o:] == 0).all()          # padding is zero
-    mod = conv_ops._param_images(w, torch.float32, 1.0, "conv", modulation=True)
+        assert f_ck == ck and d_ok == ok
+        assert f_img.shape == f_ref.shape and d_img.shape == d_ref.shape
+        assert rel_err(f_img.float(), (f_ref.float() * 0.37)) <= tol + 1e-7
+        assert rel_err(d_img.float(), (d_ref.float() * 0.37)) <= tol + 1e-7
+        assert (f_img[..., i:] == 0).all() and (d_img[..., o:] == 0).all()          # padding is zero
+    mod = wi.forward(w, torch.float32, 1.0, "conv", modulation=True)[0]
     w3 = w.detach().reshape(o, i, k * k)
-    assert torch.equal(mod["f"][0], w3.transpose(1, 2).contiguous())
-    assert torch.equal(mod["d"][0], w3.flip(-1).permute(1, 2, 0).contiguous())
-    assert rel_err(mod["wsq"], w3.square().sum(dim=2)) < 1e-6
+    assert torch.equal(mod, w3.transpose(1, 2).contiguous())
+    assert torch.equal(wi.dgrad(w, torch.float32, 1.0, "conv", modulation=True)[0], w3.flip(-1).permute(1, 2, 0).contiguous())
+    assert rel_err(wi.tap_square_sums(w), w3.square().sum(dim=2)) < 1e-6
     # cache: same object until the weight generation changes
-    assert conv_ops._param_images(w, dtype, 0.37, "conv") is conv_ops._param_images(w, dtype, 0.37, "conv")
-    conv_ops.invalidate_weight_cache()
-    assert conv_ops._param_images(w, torch.float32, 1.0, "conv", modulation=True) is not mod
+    assert wi.forward(w, dtype, 0.37, "conv") is wi.forward(w, dtype, 0.37, "conv")
+    wi.invalidate_weight_cache()
+    assert wi.forward(w, torch.float32, 1.0, "conv", modulation=True)[0] is not mod
+    # the same kernel on weights that are no Parameter -- the row-folded forward launch and the per-sample data-gradient loop
+    # of _relay_fwd / _relay_dgrad -- against the torch builders: no gain, one rounding on both sides, so exact
+    for plain, flips in (((2, 24, 16, 3, 3), (True, False)), ((24, 16, 3, 3), (False,))):
+        w = torch.randn(*plain, device=DEV)
+        assert wi._relayout_kernel_ok(w, dtype, 9)
+        f_img, ck = wi._relay_fwd(w, dtype)
+        f_ref, ck_ref = wi._torch_fwd(w, dtype)
+        assert ck == ck_ref and f_img.shape == f_ref.shape and torch.equal(f_img, f_ref)
+        for flip in flips:
+            d_img, ok = wi._relay_dgrad(w, dtype, flip=flip)
+            d_ref, ok_ref = wi._torch_dgrad(w, dtype, flip=flip)
+            assert ok == ok_ref and d_img.shape == d_ref.shape and torch.equal(d_img, d_ref)
 
 
 @pytest.mark.parametrize("m,n,k", [(16, 512, 512), (5, 7, 70), (33, 20, 1100), (1, 1, 3), (64, 129, 257)])
@@ -968,7 +981,7 @@ def test_activation_stationary_upconv_kernel(batch, hw):
     x = conv_ops.to_compute_layout(torch.randn(batch, i, h, w_, device=DEV), torch.bfloat16)
     w = (torch.randn(batch, o, i, 2, 2, device=DEV) / math.sqrt(i)).bfloat16().float()
     geo = conv_ops.Geometry("up2", 2, 2, 1, 0, (h, w_), True)
-    wk, ck = conv_ops._relay_fwd_kind(w, torch.bfloat16, "up2")
+    wk, ck = conv_ops.weight_images._relay_fwd(w, torch.bfloat16, "up2")
     assert conv_ops._fprop_plan(_lib.MSG_BF16, batch, h, w_, i, ck, h, w_, 4 * o, o, 1, 1, 1, 0, 1, 1, wk.stride(0), 0,
                                 0)[0] == _lib.MSG_PLAN_UPCONV
     y = conv_ops._f_raw(x, w, None, geo)

@@ -735,6 +735,49 @@ def test_non_square_conv_geometry_is_refused():
             conv_ops._square(bad, "stride")
 
 
+def test_weight_image_store_contract():
+    """weight_images: an image of a Parameter is kept until that parameter changes -- an in-place write, a step of the
+    optimizer that owns it, invalidate_weight_cache for it or for all -- and no longer; a different gain is a different entry;
+    a tensor that is no Parameter is never stored.  And the shapes the torch builders give."""
+    from multi_stylegan_amd import weight_images as wi
+    torch.manual_seed(0)
+    w, v = torch.nn.Parameter(torch.randn(24, 16, 3, 3)), torch.nn.Parameter(torch.randn(8, 16, 3, 3))
+
+    def image(p, gain=0.5):
+        return wi.forward(p, torch.bfloat16, gain)[0]
+    iw, iv = image(w), image(v)
+    assert image(w) is iw and image(v) is iv                                   # a second request: the same object
+    assert torch.equal(iw, wi._torch_fwd(w.detach(), torch.bfloat16)[0] * 0.5)     # (the gain after the cast, in bf16)
+    with torch.no_grad():
+        w.add_(1.0)
+    assert image(w) is not iw and image(v) is iv                               # an in-place write renews w alone
+    iw = image(w)
+    w.grad = torch.ones_like(w)
+    torch.optim.SGD([w], lr=0.1).step()
+    assert image(w) is not iw and image(v) is iv                               # the step of w's optimizer: w alone
+    iw = image(w)
+    wi.invalidate_weight_cache([v])
+    assert image(v) is not iv and image(w) is iw                               # v alone
+    iw, iv = image(w), image(v)
+    wi.invalidate_weight_cache()
+    assert image(w) is not iw and image(v) is not iv                           # both
+    iw = image(w)
+    other = image(w, 0.25)
+    assert other is not iw and image(w) is iw and image(w, 0.25) is other      # a different gain: a different entry
+    assert torch.equal(other, wi._torch_fwd(w.detach(), torch.bfloat16)[0] * 0.25)
+    plain = w.detach().clone()
+    assert image(plain) is not image(plain) and "_msg_relay" not in plain.__dict__      # no Parameter: never stored
+    assert torch.equal(image(plain), iw)
+
+    f, ck = wi._torch_fwd(w.detach(), torch.bfloat16)
+    d, ok = wi._torch_dgrad(w.detach(), torch.bfloat16, flip=True)
+    s2, ok2, taps, pad2 = wi._relay_dgrad_s2(w.detach(), torch.bfloat16, 1)
+    assert tuple(f.shape) == (24, 9, 64) and ck == 64
+    assert tuple(d.shape) == (16, 9, 64) and ok == 64
+    assert tuple(s2.shape) == (64, 4, 64) and (ok2, taps, pad2) == (64, 2, 0)
+    assert wi.dgrad(w, torch.bfloat16)[0].shape == d.shape and wi.dgrad_s2(w, torch.bfloat16, 1.0, 1)[1:] == (64, 2, 0)
+
+
 # ------------------------------------------------------------------------------ trainer surface (SURVEY 8f-3), host logic
 def _cpu_trainer(golden, **kw):
     """The product's ModelWrapper driving the CPU oracle's modules: the trainer's control flow (step order, zeroing,

@@ -18,7 +18,7 @@ b, i, o, r, k = 16, 512, 512, 256, 3
 cl = lambda t: t.contiguous(memory_format=torch.channels_last)
 xs = [cl(torch.randn(b, i, r, r, device=DEV, dtype=torch.bfloat16)) for _ in range(3)]
 w = torch.randn(b, o, i, k, k, device=DEV) / math.sqrt(i * k * k)
-wks = [conv_ops._relay_fwd(w * (1 + 0.01 * j), torch.bfloat16) for j in range(3)]
+wks = [conv_ops.weight_images._relay_fwd(w * (1 + 0.01 * j), torch.bfloat16) for j in range(3)]
 fir = (torch.outer(torch.tensor([1., 3., 3., 1.]), torch.tensor([1., 3., 3., 1.])) / 64).to(DEV)
 xb = cl(torch.randn(b, 512, 257, 257, device=DEV, dtype=torch.bfloat16))
 flops = 2.0 * b * r * r * o * i * k * k

@@ -107,7 +107,7 @@ def bench_conv(args):
             x = cl(torch.randn(b, i, r, r, device=DEV, dtype=dt))
             w = torch.randn((b, o, i, k, k) if ps else (o, i, k, k), device=DEV) / math.sqrt(i * k * k)
             g = conv_ops.Geometry(kind, k, k, s, p, (r, r), ps)
-            wk, ck = conv_ops._relay_fwd(w, dt)
+            wk, ck = conv_ops.weight_images._relay_fwd(w, dt)
             extra = int(os.environ.get("MSG_BIG_WPITCH", "0"))       # experiment: padded weight-row pitch (big kernel only)
             if extra and kind != "up2":
                 flat = wk.reshape(*wk.shape[:-2], -1)

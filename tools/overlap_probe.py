@@ -23,7 +23,7 @@ cl = lambda t: t.contiguous(memory_format=torch.channels_last)
 x = cl(torch.randn(b, i, r, r, device=DEV, dtype=torch.bfloat16))
 gy = cl(torch.randn(b, o, r, r, device=DEV, dtype=torch.bfloat16))
 w = torch.randn(b, o, i, k, k, device=DEV) / math.sqrt(i * k * k)
-wk, ck = conv_ops._relay_fwd(w, torch.bfloat16)
+wk, ck = conv_ops.weight_images._relay_fwd(w, torch.bfloat16)
 fir = (torch.outer(torch.tensor([1., 3., 3., 1.]), torch.tensor([1., 3., 3., 1.])) / 64).to(DEV)
 xb = cl(torch.randn(b, 512, 257, 257, device=DEV, dtype=torch.bfloat16))
 side = torch.cuda.Stream()

@@ -53,7 +53,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "short":
 for name, b, i, n, r, k, s, pad, shuf, ps in cases:
     x = torch.randn(b, i, r, r, device=DEV, dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
     w = torch.randn((b, n, i, k, k) if ps else (n, i, k, k), device=DEV) / math.sqrt(i * k * k)
-    wk, ck = conv_ops._relay_fwd(w, torch.bfloat16)
+    wk, ck = conv_ops.weight_images._relay_fwd(w, torch.bfloat16)
     oh = (r + 2 * pad - k) // s + 1
     fn = lambda: conv_ops._launch_fprop(x, wk, ck, None, n, (oh, oh), k, k, s, pad, 1, shuf, ps, i)
     y = fn()

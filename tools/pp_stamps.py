@@ -12,7 +12,7 @@ from multi_stylegan_amd import _lib, conv_ops
 b, i, o, r, k, st = 16, 512, 512, 256, 2, 2
 x = torch.randn(b, i, r, r, device="cuda", dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
 w = torch.randn(b, o, i, k, k, device="cuda") / math.sqrt(i * k * k)
-wk, ck = conv_ops._relay_fwd(w, torch.bfloat16)
+wk, ck = conv_ops.weight_images._relay_fwd(w, torch.bfloat16)
 for _ in range(int(os.environ.get("PP_STAMPS_LAUNCHES", "40"))):
     y = conv_ops._launch_fprop(x, wk, ck, None, o, (r // st, r // st), k, k, st, 0, 1, False, True, i)
 torch.cuda.synchronize()

@@ -44,7 +44,7 @@ for name, b, i, o, r, ps in SHAPES:
     torch.manual_seed(0)
     x = cl(torch.randn(b, i, r, r, device=DEV, dtype=torch.bfloat16))
     w = torch.randn((b, o, i, 3, 3) if ps else (o, i, 3, 3), device=DEV) / math.sqrt(9 * i)
-    wk, ck = conv_ops._relay_fwd(w, torch.bfloat16)
+    wk, ck = conv_ops.weight_images._relay_fwd(w, torch.bfloat16)
     fn = lambda: conv_ops._launch_fprop(x, wk, ck, None, o, (r, r), 3, 3, 1, 1, 1, False, ps, i)
     plan = conv_ops._fprop_plan(_lib.MSG_BF16, b, r, r, i, ck, r, r, o, o, 3, 3, 1, 1, 1, 0, wk.stride(0) if ps else 0, 0, 0)[0]
     for _ in range(3):

@@ -14,7 +14,7 @@ k = 3
 mfma_cycles = 2048 if (o >= 256 and o % 256 == 0 and i > 128) else 512     # 256 x 256 tile: 128 MFMAs of 16 cycles per wave and K-step; 128 x 128: 32
 x = torch.randn(b, i, r, r, device="cuda", dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
 w = torch.randn((b, o, i, k, k) if ps else (o, i, k, k), device="cuda") / math.sqrt(i * k * k)
-wk, ck = conv_ops._relay_fwd(w, torch.bfloat16)
+wk, ck = conv_ops.weight_images._relay_fwd(w, torch.bfloat16)
 for _ in range(200):          # long enough for the clock to settle
     y = conv_ops._launch_fprop(x, wk, ck, None, o, (r, r), k, k, 1, 1, 1, False, bool(ps), i)
 torch.cuda.synchronize()

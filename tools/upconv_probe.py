@@ -15,7 +15,7 @@ DEV = "cuda:0"
 b, i, o, r = 16, 512, 512, int(sys.argv[1]) if len(sys.argv) > 1 else 128
 x = conv_ops.to_compute_layout(torch.randn(b, i, r, r, device=DEV), torch.bfloat16)
 w = torch.randn(b, 4 * o, i, 1, 1, device=DEV) / math.sqrt(i)
-wk, ck = conv_ops._relay_fwd(w, torch.bfloat16)
+wk, ck = conv_ops.weight_images._relay_fwd(w, torch.bfloat16)
 
 
 def timeit(fn, reps=30):
