@@ -805,6 +805,50 @@ int msg_jpeg_scan_capacity(int N, int H, int W, long long* bytes);
 int msg_jpeg_encode(const unsigned char* rgb, const unsigned short* qtables, short* coef, unsigned char* scan,
                     long long* offsets, int N, int H, int W, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Metric inputs: the tensor a pretrained feature network receives from the validation pass -- select one channel, resize with
+ * anti-aliasing, map each sample to [-1, 1], replicate on the colour planes -- in one launch, or two with a normalisation.
+ * Replaces the chain of stock calls of multi_stylegan/validation_metrics.py: :44-52 (IS: kornia.resize to 299 x 299, THEN
+ * misc.normalize_m1_1_batch), :589-590 (FID: normalised frames resized to 299 x 299 inside InceptionNetworkFID.forward),
+ * :941-943 (FVD: normalised clips resized to 224 x 224 inside InceptionI3d.forward), with the frame selection and
+ * repeat_interleave(3) of :93-94, :246-247 and :451-452.
+ * images   [B, C, T, H, W] MSG_F32 or MSG_BF16, contiguous, any alignment; widened to fp32, all arithmetic fp32
+ * channel  in [0, C)
+ * t        >= 0: that time step alone (T' = 1); -1: all of them (T' = T, the FVD clip)
+ * out      [B, planes, T', out_h, out_w] MSG_F32 or MSG_BF16 (round to nearest even), whatever in_dtype is; planes 1 or 3, the
+ *          planes identical copies; every element written
+ * Resize: separable, with the weights of torch's interpolate(mode="bilinear", align_corners=False, antialias=True).  Per
+ * axis, scale = n_in / n_out, support = max(scale, 1), c = scale (i + 0.5): output i reads the taps
+ * j = max(int(c - support + 0.5), 0) .. min(int(c + support + 0.5), n_in) - 1 with w_j = max(0, 1 - |j - c + 0.5| / support),
+ * divided by the sum over the taps used.  Up-scaling is plain bilinear with border clamp; equal sizes give an exact copy.  The
+ * kernel forms the weights as integer numerators over one integer sum (w_j is (D - |n_out (2j + 1) - n_in (2i + 1)|) / D with
+ * D = 2 max(n_in, n_out)) and rounds once, and uses exactly the taps whose weight is positive.  The row-pass result lives in
+ * LDS; the source is read once per launch, plus the tiles' halo.
+ * Normalisation (misc.normalize_m1_1_batch, per sample over all selected frames): 2 max((x - lo) / (hi - lo), 1e-3) - 1 with
+ * IEEE subtract and divide, clamped from below only.
+ *   MSG_METRIC_NORM_NONE     resize and replicate only; one launch, ws may be NULL
+ *   MSG_METRIC_NORM_SOURCE   (FID, FVD) lo, hi from the sample's selected SOURCE frames; applied to every tap value before the
+ *                            filter (the clamp is not linear: it cannot be moved behind the filter)
+ *   MSG_METRIC_NORM_RESIZED  (IS) lo, hi from the sample's resized fp32 values; applied after the filter
+ * A constant sample gives 0 / 0 = NaN in all of its outputs, as the reference does; a NaN anywhere in a sample's selected frames
+ * makes that sample's whole output NaN (torch's min / max propagate NaN) and leaves the other samples alone.
+ * ws       msg_metric_input_workspace(...) BYTES, 4-byte aligned: per-workgroup (min, max) pairs, written by the first of the two
+ *          launches and read by every workgroup of the second; needs no initialisation, carries nothing between calls.
+ * No atomics, no synchronisation; a sample's result does not depend on the rest of the batch; bit-identical from run to run.
+ * 16-byte aligned images with W a multiple of 4 (fp32) / 8 (bf16) are read 16 bytes per lane, 16-byte aligned out with out_w
+ * such a multiple is stored 16 bytes per lane; anything else goes element by element, with the same bits.
+ * MSG_EINVAL: a NULL images or out, a NULL ws with a normalisation, a non-positive size, channel or t out of range, planes other
+ * than 1 or 3, an unknown norm or dtype code, more workgroups than a block index addresses.
+ * MSG_EUNSUPPORTED: n_in / n_out > MSG_METRIC_MAX_SCALE on either axis (the cap bounds the taps, 2 x the scale, and with them the
+ * LDS tile).  Nothing is launched in any of these cases; msg_metric_input_workspace returns -1 for sizes the entry refuses.
+ * ------------------------------------------------------------------------- */
+enum { MSG_METRIC_NORM_NONE = 0, MSG_METRIC_NORM_SOURCE = 1, MSG_METRIC_NORM_RESIZED = 2 };
+#define MSG_METRIC_MAX_SCALE 8
+long long msg_metric_input_workspace(int B, int T, int H, int W, int t, int out_h, int out_w, int norm);
+int msg_metric_input(const void* images, int in_dtype, int B, int C, int T, int H, int W,
+                     int channel, int t, void* out, int out_dtype, int planes,
+                     int out_h, int out_w, int norm, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,14 +16,14 @@ from .u_net_2d_discriminator import Discriminator as MultiStyleGANDiscriminator
 from .samples import (SheetWriter, dump_samples, epoch_sample_dump, interpolation_frames, interpolation_latents, sample_sheets,
                       save_prediction, write_png)
 from .tlfm_dataset import TFLMDatasetGAN, read_tiff
-from .validation_metrics import FID, FVD, IS
+from .validation_metrics import FID, FVD, IS, metric_inputs
 from .video import MjpegWriter, interpolation_video, jpeg_encode, jpeg_file, jpeg_tables
 
 __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper", "Draws", "PathLengthRegularization",
            "TopK", "AdaptiveDiscriminatorAugmentation", "AugmentationPipeline", "GeneratorSampler", "load_generator_ema", "split_sequences", "validation_samples",
            "DevicePrefetcher", "SyntheticBatches", "TLFMDeviceFeed", "prepare_tlfm_batch", "TFLMDatasetGAN", "read_tiff",
            "sample_sheets", "write_png", "SheetWriter", "save_prediction", "epoch_sample_dump", "dump_samples", "interpolation_latents",
-           "interpolation_frames", "IS", "FID", "FVD", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters",
+           "interpolation_frames", "IS", "FID", "FVD", "metric_inputs", "multi_style_gan_generator_config", "u_net_2d_discriminator_config", "generation_hyperparameters",
            "WassersteinDiscriminatorLoss", "WassersteinDiscriminatorLossCutMix", "WassersteinGeneratorLoss", "HingeGeneratorLoss",
            "HingeDiscriminatorLoss", "HingeDiscriminatorLossCutMix", "R2Regularization", "ElasticDeformation", "elastic_deformation",
            "elastic_deform_batch", "ResidentTLFMStore", "ResidentTLFMFeed", "gather_tlfm_batch", "jpeg_tables", "jpeg_encode", "jpeg_file",

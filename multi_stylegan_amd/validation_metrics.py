@@ -6,7 +6,9 @@ dataset and the EMA generator, and the statistics on the features.  What is NOT 
 reference instantiates torchvision's pretrained Inception-v3 and a pretrained I3D (validation_metrics.py:48, 571-650) whose
 weights are missing blobs of the reference repository and cannot be downloaded -- every metric class therefore takes the
 network as an argument (any ``nn.Module`` mapping a ``[B, 3, H, W]`` image / ``[B, 3, T, H, W]`` clip batch in [-1, 1] to
-features or logits); with the pretrained networks supplied the classes compute the reference's numbers.
+features or logits); with the pretrained networks supplied the classes compute the reference's numbers.  The tensor the
+network receives is made here: ``metric_inputs`` selects the channel and the time step (or the clip), resizes to the network's
+input size and normalises in the reference's order, in one ``msg_metric_input`` call (csrc/metric_input.hip) on the GPU.
 
 MI355X-first: the statistics stay on the GPU.  The reference moves every activation to the host, stacks 5000 x 2048
 arrays and calls numpy / scipy.  Here a feature sweep folds each batch into running first and second moments (float64, one
@@ -14,6 +16,7 @@ arrays and calls numpy / scipy.  Here a feature sweep folds each batch into runn
 of the SYMMETRIC matrix C_r^(1/2) C_f C_r^(1/2) (same spectrum as C_r C_f; ``eigh`` on the device, no complex arithmetic,
 eigenvalues clamped at zero where scipy's ``sqrtm(...).real`` drops an imaginary part).
 """
+import functools
 import math
 import warnings
 from typing import Iterable, Optional, Tuple, Union
@@ -22,7 +25,7 @@ import torch
 import torch.distributed as torch_dist
 import torch.nn as nn
 
-from . import misc
+from . import _lib, misc
 
 
 def _ranks() -> int:
@@ -32,7 +35,7 @@ def _ranks() -> int:
     return torch_dist.get_world_size() if torch_dist.is_available() and torch_dist.is_initialized() else 1
 
 __all__ = ["IS", "FID", "FVD", "FeatureMoments", "frechet_distance", "frechet_distance_from_moments", "inception_score",
-           "select_frames"]
+           "metric_inputs", "select_frames"]
 
 
 def select_frames(images: torch.Tensor, channel: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -45,6 +48,97 @@ def select_frames(images: torch.Tensor, channel: int, generator: Optional[torch.
 def select_clips(images: torch.Tensor, channel: int) -> torch.Tensor:
     """validation_metrics.py:451-452: the whole sequence of channel ``c`` on three colour planes: -> [B, 3, T, H, W]."""
     return images[:, channel].unsqueeze(dim=1).repeat_interleave(dim=1, repeats=3)
+
+
+# ------------------------------------------------------------------------------------------------------------ metric inputs
+def _draw_time_step(images: torch.Tensor) -> int:
+    """The draw of ``select_frames``: one ``torch.randint`` from the global CPU generator per selected batch."""
+    return int(torch.randint(0, images.shape[2], (1,)))
+
+
+_NORM_CODES = {None: "MSG_METRIC_NORM_NONE", "source": "MSG_METRIC_NORM_SOURCE", "resized": "MSG_METRIC_NORM_RESIZED"}
+
+
+@functools.lru_cache(maxsize=16)
+def _resize_weights(n_in: int, n_out: int) -> torch.Tensor:
+    """``[n_out, n_in]`` fp32: row ``i`` holds the weights of torch's ``interpolate(mode="bilinear", align_corners=False,
+    antialias=True)`` for output index ``i`` -- the triangle ``max(0, 1 - |j + 0.5 - c| / support)``, ``c = (i + 0.5) n_in / n_out``,
+    ``support = max(n_in / n_out, 1)``, over the sum of the row.  Formed as the kernel forms them (csrc/metric_input.hip): the integer
+    numerators ``D - |n_out (2j + 1) - n_in (2i + 1)|``, ``D = 2 max(n_in, n_out)``, divided by their integer sum and rounded once."""
+    i = torch.arange(n_out, dtype=torch.int64)[:, None]
+    j = torch.arange(n_in, dtype=torch.int64)[None, :]
+    u = (2 * max(n_in, n_out) - (n_out * (2 * j + 1) - n_in * (2 * i + 1)).abs()).clamp_min(0).double()
+    return (u / u.sum(dim=1, keepdim=True)).float()
+
+
+def _metric_inputs_host(x: torch.Tensor, size: Tuple[int, int], normalize: Optional[str], planes: int) -> torch.Tensor:
+    """The host's one definition, on the selected fp32 frames ``[B, T', H, W]``: the two normalisation orders around
+    ``Mh @ x @ Mw^T``."""
+    if normalize == "source":
+        x = misc.normalize_m1_1_batch(x[:, None])[:, 0]
+    x = _resize_weights(x.shape[2], size[0]).to(x.device) @ x @ _resize_weights(x.shape[3], size[1]).to(x.device).t()
+    if normalize == "resized":
+        x = misc.normalize_m1_1_batch(x[:, None])[:, 0]
+    return x[:, None].expand(-1, planes, -1, -1, -1)
+
+
+def metric_inputs(images: torch.Tensor, channel: int, t: Optional[int] = None, size: Optional[Tuple[int, int]] = None,
+                  normalize: Optional[str] = "source", planes: int = 3, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """What a pretrained feature network receives: channel ``channel`` of ``images [B, C, T, H, W]``, time step ``t`` (``None``:
+    the whole clip), resized to ``size`` (``None``: the source size), every sample mapped to [-1, 1] over all of its selected
+    frames, replicated on ``planes`` (1 or 3) colour planes: ``[B, planes, T', size[0], size[1]]`` in ``dtype`` (``None``:
+    float32; on the device float32 or bfloat16).
+
+    ``normalize``: ``"source"`` -- ``misc.normalize_m1_1_batch`` on the source frames, then the resize, the order of the
+    reference's FID and FVD (validation_metrics.py:589-590, 941-943: the networks resize what they are given);
+    ``"resized"`` -- the resize first, the order of its IS (:44-52); ``None`` -- resize only.  A constant sample is NaN
+    throughout, as in the reference, and so is a sample that holds a NaN.
+
+    The resize is torch's ``interpolate(mode="bilinear", align_corners=False, antialias=True)``: a triangle filter as wide as
+    the scale when shrinking, plain bilinear interpolation with border clamp when enlarging, a copy at equal size.  PARITY
+    UNPINNED in one respect: the reference calls ``kornia.resize(..., antialias=True)``, whose anti-aliasing is a Gaussian
+    blur in front of a plain bilinear resize.  As far as kornia's published source goes that blur is skipped when enlarging
+    (this could not be run here); if so, 256 x 256 -> 299 x 299 is plain bilinear in both and only FVD's 224 x 224 and the
+    512 x 512 configuration differ -- there by the shape of the low-pass filter.
+
+    float32 / bfloat16 tensors on the GPU go through ``msg_metric_input`` on the current stream (one launch, two with a
+    normalisation; a source side more than ``MSG_METRIC_MAX_SCALE`` = 8 times the output's is refused); CPU tensors and other dtypes take
+    one torch statement of the same definition in float32 (there a NaN without a normalisation spreads over its row and column)."""
+    if images.ndim != 5:
+        raise ValueError(f"expected [B, C, T, H, W] images, got {tuple(images.shape)}")
+    B, C, T, H, W = images.shape
+    if not 0 <= int(channel) < C:
+        raise ValueError(f"channel {channel} of {C}")
+    if t is not None and not 0 <= int(t) < T:
+        raise ValueError(f"time step {t} of {T}")
+    if planes not in (1, 3):
+        raise ValueError(f"planes is 1 or 3, not {planes}")
+    if normalize not in _NORM_CODES:
+        raise ValueError(f"normalize is 'source', 'resized' or None, not {normalize!r}")
+    size = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if min(size) < 1 or min(H, W) < 1:
+        raise ValueError(f"cannot resize {H} x {W} to {size[0]} x {size[1]}")
+    dtype = torch.float32 if dtype is None else dtype
+    images = images.detach()
+    frames = 1 if t is not None else T
+    if not (images.is_cuda and images.dtype in (torch.float32, torch.bfloat16)) or B == 0:
+        x = images[:, channel, slice(None) if t is None else slice(int(t), int(t) + 1)].to(torch.float32)
+        return _metric_inputs_host(x, size, normalize, planes).to(dtype).contiguous()
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"on the device the inputs are float32 or bfloat16, not {dtype}")
+    images = images.contiguous()
+    dev = _lib.require_gpu(images)
+    out = torch.empty((B, planes, frames, size[0], size[1]), dtype=dtype, device=dev)
+    lib, norm, t_arg = _lib.lib(), getattr(_lib, _NORM_CODES[normalize]), -1 if t is None else int(t)
+    nbytes = lib.msg_metric_input_workspace(B, T, H, W, t_arg, size[0], size[1], norm)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes > 0 else None
+    with _lib.on_device(dev):
+        with _lib.kernel_clock.span(("metric_input", images.dtype, normalize),
+                                    float(B * frames * H * W * images.element_size() + out.numel() * out.element_size())):
+            _lib.check(lib.msg_metric_input(images.data_ptr(), _lib.dtype_code(images), B, C, T, H, W, int(channel), t_arg,
+                                            out.data_ptr(), _lib.dtype_code(out), planes, size[0], size[1], norm, _lib.ptr(ws),
+                                            _lib.stream_of(dev)), "msg_metric_input")
+    return out
 
 
 class FeatureMoments:
@@ -160,20 +254,17 @@ class _Metric:
 
 class IS(_Metric):
     """Inception score of generated frames (validation_metrics.py:15-154).  ``network``: ``[B, 3, S, S]`` in [-1, 1] -> class
-    logits (the reference: torchvision's Inception-v3).  Preprocessing as :44-52 -- bilinear, anti-aliased resize to
-    ``input_size`` (299 x 299; the reference calls kornia 0.4.1's ``resize``, absent here: torch's own anti-aliased
-    interpolation stands in, PARITY UNPINNED for that one call), then the batch-wise [-1, 1] normalisation."""
+    logits (the reference: torchvision's Inception-v3).  Preprocessing as :44-52 -- channel ``c`` of one random time step,
+    the bilinear, anti-aliased resize to ``input_size`` (299 x 299; ``None``: the frames' own size), then the sample-wise
+    [-1, 1] normalisation: ``metric_inputs(..., normalize="resized")``, whose docstring says how its filter stands to
+    kornia 0.4.1's (PARITY UNPINNED when shrinking)."""
 
     def __init__(self, *args, input_size: Optional[Tuple[int, int]] = (299, 299), **kwargs) -> None:
         super().__init__(*args, **kwargs)
         self.input_size = input_size
 
-    def _preprocessing(self, frames: torch.Tensor) -> torch.Tensor:
-        x = frames[:, :, 0]
-        if self.input_size is not None and tuple(x.shape[-2:]) != tuple(self.input_size):
-            x = nn.functional.interpolate(x.float(), size=self.input_size, mode="bilinear", align_corners=False,
-                                          antialias=True)
-        return misc.normalize_m1_1_batch(x[:, :, None])[:, :, 0]
+    def _preprocessing(self, images: torch.Tensor, channel: int) -> torch.Tensor:
+        return metric_inputs(images, channel, t=_draw_time_step(images), size=self.input_size, normalize="resized")[:, :, 0]
 
     @torch.no_grad()
     def __call__(self, generator: nn.Module, **kwargs):
@@ -186,7 +277,7 @@ class IS(_Metric):
         for _ in range(math.ceil(share / self.batch_size)):
             fake_images = generator(input=self._latents(generator))
             for k, c in enumerate(channels):
-                frames = self._preprocessing(select_frames(fake_images, c))
+                frames = self._preprocessing(fake_images, c)
                 predictions[k].append(net(frames).float().softmax(dim=1))
         rows = []
         for p in predictions:
@@ -200,8 +291,12 @@ class IS(_Metric):
 
 
 class _Frechet(_Metric):
-    def __init__(self, *args, **kwargs) -> None:
+    """``input_size``: what the frames are resized to AFTER the normalisation, as the reference's networks do in their forward
+    (``metric_inputs(..., normalize="source")``); ``None`` hands the network the frames at their own size."""
+
+    def __init__(self, *args, input_size: Optional[Tuple[int, int]] = None, **kwargs) -> None:
         super().__init__(*args, **kwargs)
+        self.input_size = input_size
         self.moments_real = None                        # cached across calls like the reference's activations_real_*
 
     def _inputs(self, images: torch.Tensor, channel: int) -> torch.Tensor:
@@ -239,15 +334,17 @@ class _Frechet(_Metric):
 
 class FID(_Frechet):
     """Frechet inception distance between dataset frames and generated frames (validation_metrics.py:157-358).
-    ``network``: ``[B, 3, H, W]`` in [-1, 1] -> pooled features (the reference: Inception-v3 up to the last pooling, 2048)."""
+    ``network``: ``[B, 3, H, W]`` in [-1, 1] -> pooled features (the reference: Inception-v3 up to the last pooling, 2048).
+    ``FID(net, input_size=(299, 299))`` feeds torchvision's Inception-v3 what the reference's wrapper feeds it (:589-590)."""
 
     def _inputs(self, images, channel):
-        return misc.normalize_m1_1_batch(select_frames(images, channel))[:, :, 0]
+        return metric_inputs(images, channel, t=_draw_time_step(images), size=self.input_size, normalize="source")[:, :, 0]
 
 
 class FVD(_Frechet):
     """Frechet video distance between dataset sequences and generated sequences (validation_metrics.py:361-568).
-    ``network``: ``[B, 3, T, H, W]`` in [-1, 1] -> features of any shape (flattened per sample, :466; the reference: I3D)."""
+    ``network``: ``[B, 3, T, H, W]`` in [-1, 1] -> features of any shape (flattened per sample, :466; the reference: I3D).
+    ``FVD(net, input_size=(224, 224))`` is the reference's clip size (:941-943)."""
 
     def _inputs(self, images, channel):
-        return misc.normalize_m1_1_batch(select_clips(images, channel))
+        return metric_inputs(images, channel, t=None, size=self.input_size, normalize="source")
