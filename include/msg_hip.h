@@ -658,6 +658,37 @@ int msg_tlfm_gather(const unsigned short* frames, const unsigned int* range, lon
                     float lo1, float div1, float lo2, float div2, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Simulated datasets: a generated batch -> the 16-bit camera counts the dataset would have read it from, so that the generator's
+ * output can be written as TIFF files and read back as data.  dataset/tlfm_dataset.py:186-197 (with dataset/utils.py:4-23) read
+ * backwards: the inverse of msg_tlfm_prepare, which the reference does not have.
+ * x         [B, C, T, H, W] MSG_F32 or MSG_BF16 (widened to fp32 first), contiguous; C = 1 (bright field), 2 (+ GFP), 3 (+ RFP)
+ * bf_range  [B, T, 2] int32 in device memory: the count range (lo, hi) of every bright-field frame, 0 <= lo < hi <= 65535 (the
+ *           caller validates; other values are used as they are, the counts are clamped to [0, 65535] whatever they give)
+ * out       [B, C, T, H, W] unsigned 16-bit counts, every element written; a frame is one contiguous strip of H * W counts
+ * vflip     non-zero: output row r holds input row H - 1 - r (the dataset flips on load)
+ * All arithmetic fp32, every operation rounded on its own (no fused multiply-add):
+ *   count = (uint16) min(max(rint(fl(fl(n * scale) + offset)), 0), 65535), rint = ties to even, NaN -> 0
+ * channel 0, bf_normalise != 0: n = (x - m) / (M - m), m / M the frame's minimum / maximum over its non-NaN values (+-inf take
+ *            part as they are), IEEE subtract and correctly rounded divide; M == m: n = 0 (NaN where x is NaN);
+ *            scale = (float)(hi - lo), offset = (float) lo.  The frame's minimum writes lo, its maximum hi, exactly.
+ * channel 0, bf_normalise == 0: n = min(max(x, 0), 1), same scale and offset; no reduction, one launch.
+ * channels 1 / 2: n = min(max(x, 0), 1), scale = div1 / div2, offset = low1 / low2 -- the dataset's (gfp_min, gfp_max) /
+ *            (rfp_min, rfp_max): it divides by max, not by max - min, and so does this.
+ * ws        msg_tlfm_export_workspace(B, T) 32-bit words, read only when bf_normalise != 0; needs no initialisation and carries
+ *           nothing between calls (launch 1 writes every word launch 2 reads).  A frame is split over workgroups in row ranges
+ *           of ~4096 pixels (at most 32, at most H); fminf / fmaxf reductions, no atomics: bit-identical from run to run.
+ * W % 8 == 0 and 16-byte aligned x and out: 16-byte loads (4 fp32 / 8 bf16 pixels) and 16-byte stores (8 counts); anything else
+ * one pixel per lane with the same arithmetic.
+ * MSG_EINVAL: a non-positive size, C > 3, any other dtype, NULL x / bf_range / out, NULL ws with bf_normalise != 0, more frames
+ * and splits than the launch's block index can address.
+ * ------------------------------------------------------------------------- */
+long long msg_tlfm_export_workspace(int B, int T);
+int msg_tlfm_export(const void* x, int dtype, const int* bf_range, unsigned short* out,
+                    int B, int C, int T, int H, int W, int vflip, int bf_normalise,
+                    float low1, float div1, float low2, float div2,
+                    float* ws, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Sample output: a generated batch -> the 8-bit RGB pictures the reference writes through torchvision.utils.save_image, composed
  * in one pass.  Replaces the repeat_interleave / zero-fill / cat / permute chains, the fp32 device-to-host copy and the host
  * quantisation of multi_stylegan/misc.py:132-166 (Logger.save_prediction, called at model_wrapper.py:166-174),

@@ -15,6 +15,7 @@ from .resident import ResidentTLFMFeed, ResidentTLFMStore, gather_tlfm_batch
 from .u_net_2d_discriminator import Discriminator as MultiStyleGANDiscriminator
 from .samples import (SheetWriter, dump_samples, epoch_sample_dump, interpolation_frames, interpolation_latents, sample_sheets,
                       save_prediction, write_png)
+from .simulate import (TLFMDatasetWriter, bf_ranges_like, export_tlfm_batch, simulate_dataset, simulation_latents, write_tiff)
 from .tlfm_dataset import TFLMDatasetGAN, read_tiff
 from .validation_metrics import FID, FVD, IS, metric_inputs
 from .video import MjpegWriter, interpolation_video, jpeg_encode, jpeg_file, jpeg_tables
@@ -27,4 +28,5 @@ __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper
            "WassersteinDiscriminatorLoss", "WassersteinDiscriminatorLossCutMix", "WassersteinGeneratorLoss", "HingeGeneratorLoss",
            "HingeDiscriminatorLoss", "HingeDiscriminatorLossCutMix", "R2Regularization", "ElasticDeformation", "elastic_deformation",
            "elastic_deform_batch", "ResidentTLFMStore", "ResidentTLFMFeed", "gather_tlfm_batch", "jpeg_tables", "jpeg_encode", "jpeg_file",
-           "MjpegWriter", "interpolation_video"]
+           "MjpegWriter", "interpolation_video", "export_tlfm_batch", "write_tiff", "TLFMDatasetWriter", "bf_ranges_like",
+           "simulate_dataset", "simulation_latents"]

@@ -212,10 +212,13 @@ class SheetWriter:
         names = list(names)
         if len(names) != sheets.shape[0]:
             raise ValueError(f"{len(names)} file names for {sheets.shape[0]} sheets")
+        self._enqueue([os.path.join(self.directory, name) for name in names], sheets)
+
+    def _enqueue(self, paths: List[str], sheets: torch.Tensor) -> None:
+        """``sheets[k]`` (a uint8 batch of any trailing shape) to ``_encode(paths[k], ...)``, through the ring."""
         self._raise_pending()
-        if not names:
+        if not paths:
             return
-        paths = [os.path.join(self.directory, name) for name in names]
         if self.workers == 0:
             host = sheets.cpu().numpy()
             for path, pixels in zip(paths, host):
