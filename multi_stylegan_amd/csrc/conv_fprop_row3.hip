@@ -21,7 +21,7 @@
 // An output tile is 256 consecutive pixels = one or more whole image-row segments (map width 64, 128, or a multiple of
 // 256); segment s occupies LDS rows s*(len+2) .. s*(len+2)+len+1, i.e. output pixel p of segment s, tap kw, reads row
 // p + kw + 2 s.
-#include "conv_dispatch.h"
+#include "conv_epilogue.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -458,32 +458,24 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 1) void conv_fprop_row3_kernel(c
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the dummy pieces of the last step write zeros: they must land first)
     __syncthreads();
 
-    // ---- epilogue: wave-private WM x WN bf16 patch in LDS, then 16-B stores.  Transposed accumulators: lane (lr, lh)
-    // owns pixel 32 i + lr and, per group g = e >> 2, the four CONSECUTIVE channels 32 j + 8 g + 4 lh + (0..3): one packed
-    // 8-byte LDS write each; 8-byte unit u of row r lives at unit u ^ (r & 15).
-    constexpr int PITCH = WN * ESZ;
-    char* ep = smem + wid * (WM * PITCH);
-    // (S16: lane (lr, lh) owns pixel 16 i + lr and the four channels 16 j + 4 lh + (0..3) of block (i, j): G = 1 group)
-    constexpr int G = S16 ? 1 : 4;
+    // ---- epilogue (conv_epilogue.h): accumulators + bias -> wave-private WM x WN bf16 patch -> 16-B stores
+    char* ep = smem + wid * (WM * WN * ESZ);
+    constexpr int G = S16 ? 1 : 4;                              // groups of four channels a lane owns in one block
 #pragma unroll
     for (int j = 0; j < NB; ++j)
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const int unit = S16 ? 4 * j + lh : 8 * j + 2 * g + lh;
-            float bv[4] = {0.f, 0.f, 0.f, 0.f};
+            f32x4 bv = {0.f, 0.f, 0.f, 0.f};
             if (bias) {
                 const int nb = n0 + wn * WN + 4 * unit;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) bv[e] = bias[nb + e];              // (N % HN == 0: eligibility)
             }
 #pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                const int row = i * BLK + lr;
-                uint2 pk;
-                pk.x = (unsigned)f2bf(acc[i][j][4 * g + 0] + bv[0]) | ((unsigned)f2bf(acc[i][j][4 * g + 1] + bv[1]) << 16);
-                pk.y = (unsigned)f2bf(acc[i][j][4 * g + 2] + bv[2]) | ((unsigned)f2bf(acc[i][j][4 * g + 3] + bv[3]) << 16);
-                *reinterpret_cast<uint2*>(ep + row * PITCH + ((unit ^ (row & 15)) << 3)) = pk;
-            }
+            for (int i = 0; i < NA; ++i)
+                conv_patch_write<bf16_t, WN>(ep, i * BLK + lr, unit,
+                                             f32x4{acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]}, bv);
         }
     constexpr int LPR = WN / VEC;                               // lanes per patch row: 16 / 8
     constexpr int RPP = 64 / LPR;                               // rows per pass: 4 / 8
@@ -513,11 +505,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 1) void conv_fprop_row3_kernel(c
             }
             if (half == 0) __syncthreads();
             u32x4 v[NP];
-#pragma unroll
-            for (int pass = 0; pass < NP; ++pass) {
-                const int row = half * 64 + pass * RPP + er;
-                v[pass] = *reinterpret_cast<const u32x4*>(ep + row * PITCH + ((u16 ^ ((row & 15) >> 1)) << 4));
-            }
+            conv_patch_read<bf16_t, WN, NP, RPP>(ep, half * 64 + er, u16, v);
             unsigned sbits[NP];
             if (p.act.mask) {
 #pragma unroll
@@ -539,10 +527,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 1) void conv_fprop_row3_kernel(c
                 for (int pass = 0; pass < NP; ++pass)
                     r[pass] = *reinterpret_cast<const u32x4*>(rrow + (long long)(pass * RPP) * p.act.res_ld);
             }
-            if (er & 1) {
-#pragma unroll
-                for (int pass = 0; pass < NP; ++pass) v[pass] = u32x4{v[pass][2], v[pass][3], v[pass][0], v[pass][1]};
-            }
+            conv_patch_swap_odd<NP>(er, v);
 #pragma unroll
             for (int pass = 0; pass < NP; ++pass) {
 #pragma clang fp contract(off)
@@ -604,15 +589,8 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 1) void conv_fprop_row3_kernel(c
         }
         if (half == 0) __syncthreads();
         u32x4 v[NP];
-#pragma unroll
-        for (int pass = 0; pass < NP; ++pass) {
-            const int row = half * 64 + pass * RPP + er;
-            v[pass] = *reinterpret_cast<const u32x4*>(ep + row * PITCH + ((u16 ^ ((row & 15) >> 1)) << 4));
-        }
-        if (er & 1) {
-#pragma unroll
-            for (int pass = 0; pass < NP; ++pass) v[pass] = u32x4{v[pass][2], v[pass][3], v[pass][0], v[pass][1]};
-        }
+        conv_patch_read<bf16_t, WN, NP, RPP>(ep, half * 64 + er, u16, v);
+        conv_patch_swap_odd<NP>(er, v);
         if (p.act.enabled == 1) {
             if (p.act.alpha >= 0.f && p.act.alpha <= 1.f) {
 #pragma unroll

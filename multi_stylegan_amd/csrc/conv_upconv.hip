@@ -25,9 +25,9 @@
 //     wave-private LDS patch -> 16-byte stores of whole 128-byte channel runs) runs beside the other waves' MFMAs, and the
 //     chip's stores spread over time instead of arriving in bursts.
 // Accumulators: a wave tile is 128 pixels x 64 columns (4 x 2 blocks of 32 x 32, 128 registers), operands swapped so that a
-// lane owns a pixel and four consecutive channels (see conv_fprop_pp.hip's epilogue).  One workgroup of EIGHT waves per CU
+// lane owns a pixel and four consecutive channels (conv_epilogue.h).  One workgroup of EIGHT waves per CU
 // (two per SIMD, <= 256 registers each), all 160 KiB of its LDS: 128 KiB activations + eight 4-KiB epilogue patches.
-#include "conv_dispatch.h"
+#include "conv_epilogue.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
@@ -143,9 +143,8 @@ __global__ __launch_bounds__(64 * UC_WAVES, 1) void conv_upconv_kernel(const bf1
             }
         }
 
-        // ---- epilogue of the slice: 32 pixels at a time through the wave's patch.  Lane (lr, lh) owns pixel 32 i + lr and, per
-        // group g = e >> 2, channels 32 j + 8 g + 4 lh + (0..3): one packed 8-byte write; 8-byte unit u of row r lives at
-        // unit u ^ (r & 15).  Read back as 16-byte vectors, 8 lanes per 128-byte pixel row, 8 rows per pass.
+        // ---- epilogue of the slice (conv_epilogue.h): 32 pixels x 64 channels at a time through the wave's patch, read back 8
+        // rows per pass
         const int q = n0 / p.O, c0 = n0 - q * p.O;             // sub-pixel position (dy, dx) and first channel of the slice
         const int dy = q >> 1, dx = q & 1;
         const int er = lane >> 3, ec = lane & 7;
@@ -154,21 +153,13 @@ __global__ __launch_bounds__(64 * UC_WAVES, 1) void conv_upconv_kernel(const bf1
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int unit = 8 * j + 2 * g + lh;
-                    uint2 pk;
-                    pk.x = (unsigned)f2bf(acc[i][j][4 * g + 0]) | ((unsigned)f2bf(acc[i][j][4 * g + 1]) << 16);
-                    pk.y = (unsigned)f2bf(acc[i][j][4 * g + 2]) | ((unsigned)f2bf(acc[i][j][4 * g + 3]) << 16);
-                    *reinterpret_cast<uint2*>(patch + lr * 128 + ((unit ^ (lr & 15)) << 3)) = pk;
-                }
+                for (int g = 0; g < 4; ++g)
+                    conv_patch_write<bf16_t, 64>(patch, lr, 8 * j + 2 * g + lh,
+                                                 f32x4{acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]});
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (wave-private patch: the wave's own writes have landed)
             u32x4 v[4];
-#pragma unroll
-            for (int pass = 0; pass < 4; ++pass) {
-                const int row = pass * 8 + er;
-                v[pass] = *reinterpret_cast<const u32x4*>(patch + row * 128 + ((ec ^ ((row & 15) >> 1)) << 4));
-                if (row & 1) v[pass] = u32x4{v[pass][2], v[pass][3], v[pass][0], v[pass][1]};
-            }
+            conv_patch_read<bf16_t, 64, 4, 8>(patch, er, ec, v);
+            conv_patch_swap_odd<4>(er, v);
 #pragma unroll
             for (int pass = 0; pass < 4; ++pass) {
                 const int m = m0 + 32 * i + pass * 8 + er;

@@ -681,9 +681,9 @@ def _worst_element(got, ref):
     return {"worst (sample, channel, row, column)": at, "got": float(got[at]), "want": float(ref[at])}
 
 
-def _clocked(fn, want_kernel):
+def _clocked(fn, want_kernel, storage="bf16"):
     """fn() with the kernel clock on: its result, after asserting that the ONE launch of the forward family it made carries the
-    clock label of the MSG_PLAN_* kernel named `want_kernel` (conv_ops._PLANS)."""
+    clock label of the MSG_PLAN_* kernel named `want_kernel` (conv_ops._PLANS) and of the storage type `storage`."""
     from multi_stylegan_amd import _lib, conv_ops
     _lib.kernel_clock.reset(enabled=True)
     try:
@@ -693,7 +693,7 @@ def _clocked(fn, want_kernel):
     finally:
         _lib.kernel_clock.reset(enabled=False)
     label = conv_ops._PLANS[getattr(_lib, "MSG_PLAN_" + want_kernel)][0]
-    assert ran == {label + "/bf16": 1}, (want_kernel, ran)
+    assert ran == {label + "/" + storage: 1}, (want_kernel, ran)
     return out
 
 
@@ -766,6 +766,40 @@ def test_large_tile_kernel_epilogues_against_float64(name):
         e = rel_err(y.float(), ref)
         print(f"\n{c.name}: {leg} {c.fwd} rel_err {e:.3e} (bound {tol:g})")
         assert e < tol, (leg, e, _worst_element(y.float(), ref))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("shape,kernel", [((2, 40, 72, 13, 11, 3), "DMA"), ((3, 24, 136, 9, 9, 1), "REG")], ids=["3x3_dma", "1x1_reg"])
+def test_conv_residual_merge_matches_two_pass(shape, kernel, dtype):
+    """conv_ops.conv2d_add_residual, the discriminator's residual merge in the epilogue of the 128 x 128 kernels, == conv2d followed
+    by scaled_add, bit for bit (msg_common.h: residual_epilogue_apply is scaled_add's arithmetic on the rounded conv result); its
+    first-order gradients against the float64 form.  3x3: 286 GEMM rows (three M tiles, the last ragged), >= 9 K-steps: LDS-DMA
+    staging.  1x1: 243 rows, two N tiles, the second 8 columns wide, one K-step: register staging (bf16: the lean instantiation)."""
+    from multi_stylegan_amd import conv_ops
+    from multi_stylegan_amd.op_static import scaled_add
+    b, i, o, h, w_, k = shape
+    gain, tol, storage = 1 / math.sqrt(2), TOLS[dtype], "bf16" if dtype == torch.bfloat16 else "f32"
+    g = torch.Generator().manual_seed(sum(shape))
+    x = torch.randn(b, i, h, w_, generator=g).to(dtype)
+    w = torch.randn(o, i, k, k, generator=g) / math.sqrt(i * k * k)
+    main = torch.randn(b, o, h, w_, generator=g).to(dtype)
+    gy = torch.randn(b, o, h, w_, generator=g).to(dtype)
+    xd, md = (t.to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_(True) for t in (x, main))
+    wd = w.to(DEV).requires_grad_(True)
+    y = _clocked(lambda: conv_ops.conv2d_add_residual(xd, wd, md, gain, padding=k // 2, wscale=0.7), kernel, storage)
+    conv = _clocked(lambda: conv_ops.conv2d(xd, wd, None, padding=k // 2, wscale=0.7), kernel, storage)
+    two_pass = scaled_add(conv, md, gain)
+    assert y.shape == two_pass.shape and y.dtype == dtype
+    assert torch.equal(y, two_pass), ("forward", rel_err(y.float(), two_pass.float()))
+    xr, wr, mr = (t.double().requires_grad_(True) for t in (x, w, main))
+    yr = (F.conv2d(xr, 0.7 * wr, padding=k // 2) + mr) * gain
+    refs = torch.autograd.grad(yr, (xr, wr, mr), gy.double())
+    grads = torch.autograd.grad(y, (xd, wd, md), gy.to(DEV).contiguous(memory_format=torch.channels_last))
+    assert rel_err(y.float(), yr.detach()) < tol, "forward against float64"
+    for name, got, ref in zip(("x", "w", "main"), grads, refs):
+        e = rel_err(got.float(), ref)
+        print(f"\n{shape} {storage}: gradient {name} rel_err {e:.3e} (bound {tol:g})")
+        assert got.shape == ref.shape and e < tol, ("gradient", name, e)
 
 
 @pytest.mark.parametrize("b", [31, 33], ids=["just_below_2GiB", "above_2GiB"])
