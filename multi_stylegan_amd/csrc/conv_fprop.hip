@@ -20,13 +20,6 @@
 #include "conv_epilogue.h"
 #include <stdlib.h>
 
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-// explicit global-address-space pointers: loads through them are global_load (never flat_load, which would force a
-// vmcnt(0) in front of every LDS access and serialise the pipeline)
-typedef const __attribute__((address_space(1))) char* gptr_t;
-typedef const __attribute__((address_space(1))) u32x4* gvec_t;
-typedef __attribute__((address_space(3))) char* lds_t;
-
 struct ConvParams {
     int B, IH, IW, Cx, Ck, OH, OW, N, ldy;
     int kh, kw, stride, pad, in_up, pixel_shuffle, per_sample;
@@ -60,26 +53,7 @@ __device__ __forceinline__ int swz(int row, int slot) { return row * ROWB + ((sl
 // down to 2^-16 of the leading product.  (The first version split the fragments inside the MFMA loop, every wave its own copy
 // of every operand: 5.5 vector instructions per element and sub-step made the six-product kernel 1.13x the speed of the exact
 // fp32 MFMA instead of the 2.7x its matrix time allows.)  Register staging only (LDS-DMA cannot convert in flight).
-// four floats -> SPLIT x (four bf16 = 8 bytes)
-template <int SPLIT>
-__device__ __forceinline__ void split_park(const u32x4& raw, char* dst) {
-    uint2 pl[3];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float x0 = __uint_as_float(raw[2 * h]), x1 = __uint_as_float(raw[2 * h + 1]);
-        const unsigned hp = (unsigned)f2bf(x0) | ((unsigned)f2bf(x1) << 16);
-        const float r0 = x0 - __uint_as_float(hp << 16), r1 = x1 - __uint_as_float(hp & 0xffff0000u);
-        const unsigned mp = (unsigned)f2bf(r0) | ((unsigned)f2bf(r1) << 16);
-        (h ? pl[0].y : pl[0].x) = hp;
-        (h ? pl[1].y : pl[1].x) = mp;
-        if constexpr (SPLIT == 3) {
-            const float q0 = r0 - __uint_as_float(mp << 16), q1 = r1 - __uint_as_float(mp & 0xffff0000u);
-            (h ? pl[2].y : pl[2].x) = (unsigned)f2bf(q0) | ((unsigned)f2bf(q1) << 16);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < SPLIT; ++p) *reinterpret_cast<uint2*>(dst + p * 64) = pl[p];
-}
+// The split itself is msg_split_park (msg_common.h), planes 64 bytes apart inside a row.
 
 template <typename T, bool DMA, int LEAN = 0, int SPLIT = 0>
 __global__ __launch_bounds__(256, LEAN ? LEAN : 2) void conv_fprop_kernel(const T* __restrict__ x, const T* __restrict__ w,
@@ -246,8 +220,8 @@ __global__ __launch_bounds__(256, LEAN ? LEAN : 2) void conv_fprop_kernel(const 
             char* sb = sa + BM * SROW;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {                       // floats 4 slot .. 4 slot + 3 of the row -> 8 bytes per plane
-                split_park<SPLIT>(ra[j], sa + row_of[j] * SROW + slot_phys * 8);
-                split_park<SPLIT>(rb[j], sb + row_of[j] * SROW + slot_phys * 8);
+                msg_split_park<SPLIT>(ra[j], sa + row_of[j] * SROW + slot_phys * 8, 64);
+                msg_split_park<SPLIT>(rb[j], sb + row_of[j] * SROW + slot_phys * 8, 64);
             }
             return;
         }

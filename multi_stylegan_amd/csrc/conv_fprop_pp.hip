@@ -30,8 +30,6 @@
 #include "conv_epilogue.h"
 #include <stdlib.h>
 
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char* lds_t;
 
 struct ConvParamsPP {
     int B, IH, IW, Cx, Ck, OH, OW, N, ldy;

@@ -25,9 +25,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char* lds_t;
-
 struct ConvParamsR3 {
     int B, IH, IW, Cx, Ck, OH, OW, N, ldy;
     int per_sample, seg_len, n_seg;
@@ -39,7 +36,6 @@ struct ConvParamsR3 {
 };
 
 constexpr int HROW = 128;
-constexpr int H_OOB = (int)0x80000000;
 
 #ifdef MSG_ROW3_STAMPS
 // diagnostic build only (tools/row3_stamps.py; never ship or benchmark it): cycle stamps of K-steps 9..11 of every wave
@@ -220,7 +216,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 1) void conv_fprop_row3_kernel(c
         const int tap_off = kh * p.IW * p.Cx * ESZ;
         const unsigned bad = kh >= 3 ? ~0u : (~a_flags | (kh == 0 ? a_flags >> 9 : 0u) | (kh == 2 ? a_flags >> 18 : 0u));
 #pragma unroll
-        for (int j = 0; j < NAP + 1; ++j) va[j] = ((bad >> j) & 1u) ? H_OOB : a_b32[j] + tap_off;
+        for (int j = 0; j < NAP + 1; ++j) va[j] = ((bad >> j) & 1u) ? MSG_DMA_OOB : a_b32[j] + tap_off;
     };
     // activation piece j of (kh set by set_kh, chunk) into activation buffer `abuf`
     auto dma_a = [&](int j, int abuf, int chunk) __attribute__((always_inline)) {
@@ -234,7 +230,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 1) void conv_fprop_row3_kernel(c
     auto dma_b = [&](int j, int bbuf, int tap, int chunk, bool live) __attribute__((always_inline)) {
         lds_t la = (lds_t)(smem + 2 * HA + bbuf * HB + (wid_u * (WN / 2) + 8 * j) * HROW);
 #if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, la, 16, live ? vb2[j & 1] : H_OOB,
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, la, 16, live ? vb2[j & 1] : MSG_DMA_OOB,
                                                  (tap * p.n_chunks + chunk) * HROW + (j >> 1) * w_piece2, 0, 0);
 #endif
     };

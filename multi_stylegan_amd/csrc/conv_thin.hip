@@ -20,7 +20,6 @@
 #include "conv_dispatch.h"
 #include <stdlib.h>
 
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
 typedef float f32v4 __attribute__((ext_vector_type(4)));
 
 struct ThinParams {

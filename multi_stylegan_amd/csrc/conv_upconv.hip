@@ -30,9 +30,6 @@
 #include "conv_epilogue.h"
 #include <stdlib.h>
 
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-typedef const __attribute__((address_space(1))) char* gptr_t;
-typedef __attribute__((address_space(3))) char* lds_t;
 
 struct UpconvParams {
     int B, H, W, Cx, N, O, ldy;

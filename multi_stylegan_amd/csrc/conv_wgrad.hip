@@ -22,14 +22,9 @@
 // the kernel); other maps take the generic incremental addressing.
 // pixel_shuffle = 1 is the weight gradient of the generator's 2x2 stride-2 transposed conv: tap (dy,dx) pairs
 // X[b,h,w,:] with GY[b, 2h+dy, 2w+dx, :].
-#include "conv_dispatch.h"
+#include "conv_wgrad_tile.h"
 #include <stdlib.h>
 
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) char* gptr_t;       // explicit global pointers: global_load, never flat
-typedef const __attribute__((address_space(1))) u32x4* gvec_t;
-typedef __attribute__((address_space(3))) char* lds_t;
 __device__ __attribute__((aligned(256))) unsigned int g_wgrad_zero_page[64];   // rows that must contribute zeros read here
 
 struct WgradParams {
@@ -51,11 +46,6 @@ struct WgradParams {
 
 constexpr int WT = 128;                              // tile extent in both channel dimensions
 template <typename T> struct WgCfg { static constexpr int KP = 8192 / (WT * sizeof(T)) * 2; };  // 64 bf16 / 32 f32
-// byte offset of 16-B chunk `ch` of pixel row `r` inside a [KP][128] tile, rows rotated by 64 B * (r & 3)
-template <typename T> __device__ __forceinline__ int wg_off(int r, int ch) {
-    constexpr int ROW = WT * sizeof(T);
-    return r * ROW + (((ch << 4) + ((r & 3) << 6)) & (ROW - 1));
-}
 
 // UNI ("uniform rows"): when a K-step of KP pixels never straddles output rows unevenly (OW divides KP or KP divides
 // OW -- every power-of-two map), each thread's pixel sits at a FIXED (row, column) displacement from the K-step's first
@@ -63,33 +53,12 @@ template <typename T> __device__ __forceinline__ int wg_off(int r, int ch) {
 // the loads become buffer loads (descriptor = sample base, voffset = constant, soffset = scalar): out-of-image rows
 // get an out-of-range voffset, for which the hardware returns zeros.  This removes ~170 of the ~200 VALU instructions
 // per K-step that the generic incremental addressing costs (the kernel was VALU-bound: 12 VALU per MFMA).
-constexpr int BUF_OOB = (int)0x80000000;             // voffset >= num_records: the buffer load returns 0
+// (MSG_DMA_OOB, msg_common.h, is such an out-of-range voffset: >= num_records, the buffer load returns 0.)
 
 // SPLIT = 3 (T = float; MSG_F32_SPLIT): products as bf16 MFMAs on splits of the fp32 operands, see
-// conv_fprop.hip / msg_hip.h.  As there, the split happens once per element on the way from the staging registers into LDS:
-// the K-step's image is SPLIT bf16 planes per operand, each laid out exactly like the bf16 kernel's [pixel][channel] tile
-// (256-byte rows, 64-byte rotation), so the fragments come from the same transposing reads.
-// four floats -> SPLIT x (four bf16 = 8 bytes), plane p at dst + p * plane_bytes
-template <int SPLIT>
-__device__ __forceinline__ void wg_split_park(const u32x4& raw, char* dst, int plane_bytes) {
-    uint2 pl[3];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float x0 = __uint_as_float(raw[2 * h]), x1 = __uint_as_float(raw[2 * h + 1]);
-        const unsigned hp = (unsigned)f2bf(x0) | ((unsigned)f2bf(x1) << 16);
-        const float r0 = x0 - __uint_as_float(hp << 16), r1 = x1 - __uint_as_float(hp & 0xffff0000u);
-        const unsigned mp = (unsigned)f2bf(r0) | ((unsigned)f2bf(r1) << 16);
-        (h ? pl[0].y : pl[0].x) = hp;
-        (h ? pl[1].y : pl[1].x) = mp;
-        if constexpr (SPLIT == 3) {
-            const float q0 = r0 - __uint_as_float(mp << 16), q1 = r1 - __uint_as_float(mp & 0xffff0000u);
-            (h ? pl[2].y : pl[2].x) = (unsigned)f2bf(q0) | ((unsigned)f2bf(q1) << 16);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < SPLIT; ++p) *reinterpret_cast<uint2*>(dst + p * plane_bytes) = pl[p];
-}
-
+// conv_fprop.hip / msg_hip.h.  As there, the split happens once per element on the way from the staging registers into LDS
+// (msg_split_park): the K-step's image is SPLIT bf16 planes per operand, each laid out exactly like the bf16 kernel's
+// [pixel][channel] tile (256-byte rows, 64-byte rotation), so the fragments come from the same transposing reads.
 template <typename T, bool DMA, bool UNI, int SPLIT = 0>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict__ gy, const T* __restrict__ x,
                                                             float* __restrict__ gw, float* __restrict__ ws, WgradParams p) {
@@ -157,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
     const int wid_u = __builtin_amdgcn_readfirstlane(wid);
     const int r0 = DMA ? (wid * RPW + lane / CPR) : tid / CPR;
     const int ch_phys = DMA ? (lane % CPR) : (tid % CPR);
-    const int ch = DMA ? ((ch_phys - 4 * (r0 & 3)) & (CPR - 1)) : ch_phys;   // (row & 3) is the same for all j: steps of 4*RPW rows
+    const int ch = DMA ? wg_dma_chunk<ROW>(r0, ch_phys) : ch_phys;   // (row & 3) is the same for all j: steps of 4*RPW rows
     const gptr_t zsrc = (gptr_t)g_wgrad_zero_page + (tid & 7) * 16;
     // K-step stride in (sample, row, column) units; without folding a step never leaves its sample
     const int step_b = p.fold ? KP / npix : 0;
@@ -179,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
     }
     int st_off[NLD];
 #pragma unroll
-    for (int j = 0; j < NLD; ++j) st_off[j] = wg_off<T>(r0 + (DMA ? 4 * RPW : RSTEP) * j, ch);
+    for (int j = 0; j < NLD; ++j) st_off[j] = wg_image_off<ROW>(r0 + (DMA ? 4 * RPW : RSTEP) * j, ch << 4);
 
     // ---- UNI staging state: thread constants (VGPR) + wave-uniform cursor (SGPR)
     const int u_gs = p.pixel_shuffle ? 2 : 1, u_gkh = p.pixel_shuffle ? kh_ : 0, u_gkw = p.pixel_shuffle ? kw_ : 0;
@@ -193,8 +162,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
     if constexpr (UNI) {
         const char* gbase = (const char*)gy + (long long)b * gyh * gyw * u_L;
         const char* xbase = (const char*)x + (long long)b * p.IH * p.IW * u_C + ((long long)u_xkh * p.IW + u_xkw) * u_C;
-        rs_gy = __builtin_amdgcn_make_buffer_rsrc((void*)gbase, 0, BUF_OOB, 0x00020000);
-        rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, BUF_OOB, 0x00020000);
+        rs_gy = __builtin_amdgcn_make_buffer_rsrc((void*)gbase, 0, MSG_DMA_OOB, 0x00020000);
+        rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, MSG_DMA_OOB, 0x00020000);
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             const int r = r0 + RSTEP * j;
@@ -202,8 +171,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
             const int rr = r - db * npix;
             const int dh = rr / owl, dw = rr - dh * owl;
             dw_c[j] = dw;
-            voff_gy[j] = oc_ok ? db * gy_sample + (dh * u_gs * gyw + dw * u_gs) * u_L + oc * (int)sizeof(T) : BUF_OOB;
-            voff_x[j] = ic_ok ? db * x_sample + (dh * u_xs * p.IW + dw * u_xs) * u_C + ic * (int)sizeof(T) : BUF_OOB;
+            voff_gy[j] = oc_ok ? db * gy_sample + (dh * u_gs * gyw + dw * u_gs) * u_L + oc * (int)sizeof(T) : MSG_DMA_OOB;
+            voff_x[j] = ic_ok ? db * x_sample + (dh * u_xs * p.IW + dw * u_xs) * u_C + ic * (int)sizeof(T) : MSG_DMA_OOB;
             xh_c[j] = dh * u_xs;
             xw_c[j] = dw * u_xs;
         }
@@ -237,8 +206,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
                 const bool pok = (r0 + RSTEP * j < rem) & (col_s + dw_c[j] < p.OW) & (row_s * u_xs + xh_c[j] < p.OH * u_xs);
                 const bool xok = pok & ((unsigned)(xh_s + xh_c[j]) < (unsigned)p.IH) &
                                  ((unsigned)(xw_s + xw_c[j]) < (unsigned)p.IW);
-                ra[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_gy, pok ? voff_gy[j] : BUF_OOB, so_gy, 0);
-                rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, xok ? voff_x[j] : BUF_OOB, so_x, 0);
+                ra[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_gy, pok ? voff_gy[j] : MSG_DMA_OOB, so_gy, 0);
+                rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, xok ? voff_x[j] : MSG_DMA_OOB, so_x, 0);
             }
             pix_s += KP;
             b_s += step_b;
@@ -284,9 +253,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
 #pragma unroll
             for (int j = 0; j < NLD; ++j) {
                 const int r = r0 + RSTEP * j;              // channels 4 ch .. 4 ch + 3 of pixel row r -> 8 bytes per plane
-                const int off = r * PROW + ((ch * 8 + ((r & 3) << 6)) & (PROW - 1));
-                wg_split_park<SPLIT>(ra[j], st + off, PTILE);
-                wg_split_park<SPLIT>(rb[j], st + SPLIT * PTILE + off, PTILE);
+                const int off = wg_image_off<PROW>(r, ch * 8);
+                msg_split_park<SPLIT>(ra[j], st + off, PTILE);
+                msg_split_park<SPLIT>(rb[j], st + SPLIT * PTILE + off, PTILE);
             }
             return;
         }
@@ -331,35 +300,21 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
             const char* sa = smem + (ONE_STAGE ? 0 : (it & 1) * SSTAGE);
             const char* sb = sa + TILE;
             if constexpr (sizeof(T) == 2) {
-                // transposed fragment: lane = 16 g + 4 q + pq supplies the address of pixel row (kb + q), channels
-                // cb + 4 pq ..+3; it receives channel (cb + lane%16) of pixel rows kb .. kb+3.
-                const int g = lane >> 4, q = (lane >> 2) & 3, pq = lane & 3;
-                const int kb = 8 * (g >> 1), cb = 16 * (g & 1);
-                typedef short s16x8 __attribute__((ext_vector_type(8)));
-                auto frag = [&](const char* base, int ks, int col0) __attribute__((always_inline)) {
-                    s16x4 part[2];
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        const int r = ks * 16 + kb + 4 * half + q;
-                        const char* pa = base + r * ROW + (((col0 + cb + 4 * pq) * 2 + ((r & 3) << 6)) & (ROW - 1));
-                        part[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pa));
-                    }
-                    return __builtin_bit_cast(bf16v8, (s16x8)__builtin_shufflevector(part[0], part[1], 0, 1, 2, 3, 4, 5, 6, 7));
-                };
+                // transposed fragments (wg_frag, conv_wgrad_tile.h)
                 constexpr int NKS = KP / 16;
                 bf16v8 fa[2][2], fb[2][2];
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    fa[0][t] = frag(sa, 0, wm * 64 + t * 32);
-                    fb[0][t] = frag(sb, 0, wn * 64 + t * 32);
+                    fa[0][t] = wg_frag(sa, lane, 0, wm * 64 + t * 32);
+                    fb[0][t] = wg_frag(sb, lane, 0, wn * 64 + t * 32);
                 }
 #pragma unroll
                 for (int ks = 0; ks < NKS; ++ks) {                  // k-steps of 16 pixels, fragments one step ahead
                     if (ks + 1 < NKS) {
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
-                            fa[(ks + 1) & 1][t] = frag(sa, ks + 1, wm * 64 + t * 32);
-                            fb[(ks + 1) & 1][t] = frag(sb, ks + 1, wn * 64 + t * 32);
+                            fa[(ks + 1) & 1][t] = wg_frag(sa, lane, ks + 1, wm * 64 + t * 32);
+                            fb[(ks + 1) & 1][t] = wg_frag(sb, lane, ks + 1, wn * 64 + t * 32);
                         }
                     }
 #pragma unroll
@@ -376,19 +331,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
                 __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             } else if constexpr (SPLIT != 0) {
                 // SPLIT bf16 planes per operand, each a [KP][128] bf16 tile: the bf16 kernel's transposing fragment reads
-                const int g = lane >> 4, q = (lane >> 2) & 3, pq = lane & 3;
-                const int kb = 8 * (g >> 1), cb = 16 * (g & 1);
-                typedef short s16x8 __attribute__((ext_vector_type(8)));
-                auto frag = [&](const char* base, int ks, int col0) __attribute__((always_inline)) {
-                    s16x4 part[2];
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        const int r = ks * 16 + kb + 4 * half + q;
-                        const char* pa = base + r * PROW + (((col0 + cb + 4 * pq) * 2 + ((r & 3) << 6)) & (PROW - 1));
-                        part[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pa));
-                    }
-                    return __builtin_bit_cast(bf16v8, (s16x8)__builtin_shufflevector(part[0], part[1], 0, 1, 2, 3, 4, 5, 6, 7));
-                };
                 const char* sbp = sa + SPLIT * PTILE;
 #pragma unroll
                 for (int ks = 0; ks < KP / 16; ++ks) {
@@ -397,8 +339,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
                     for (int t = 0; t < 2; ++t)
 #pragma unroll
                         for (int pl = 0; pl < SPLIT; ++pl) {
-                            af[pl][t] = frag(sa + pl * PTILE, ks, wm * 64 + t * 32);
-                            bfr[pl][t] = frag(sbp + pl * PTILE, ks, wn * 64 + t * 32);
+                            af[pl][t] = wg_frag(sa + pl * PTILE, lane, ks, wm * 64 + t * 32);
+                            bfr[pl][t] = wg_frag(sbp + pl * PTILE, lane, ks, wn * 64 + t * 32);
                         }
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
@@ -417,12 +359,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
 #pragma unroll 4
                 for (int ks = 0; ks < KP / 2; ++ks) {              // k-steps of 2 pixels
                     const int r = 2 * ks + lh;
-                    const int rot = (r & 3) << 6;
                     float fa[2], fb[2];
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        fa[t] = *reinterpret_cast<const float*>(sa + r * ROW + (((wm * 64 + t * 32 + lr) * 4 + rot) & (ROW - 1)));
-                        fb[t] = *reinterpret_cast<const float*>(sb + r * ROW + (((wn * 64 + t * 32 + lr) * 4 + rot) & (ROW - 1)));
+                        fa[t] = *reinterpret_cast<const float*>(sa + wg_image_off<ROW>(r, (wm * 64 + t * 32 + lr) * 4));
+                        fb[t] = *reinterpret_cast<const float*>(sb + wg_image_off<ROW>(r, (wn * 64 + t * 32 + lr) * 4));
                     }
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
@@ -437,24 +378,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const T* __restrict_
     // ---- epilogue: fp32, lanes 0..31 = 32 consecutive input channels (128-B runs)
     const int lr = lane & 31, lh = lane >> 5;
     const int taps = p.kh * p.kw;
-    // a K-slice of a split sum owns slab z of the workspace (kernel layout, every element written: zeros included)
-    float* gz = p.split ? ws + (long long)z * p.slab : gw + (p.per_sample ? (long long)b * p.gw_zstride : 0);
-    const bool oi_major = p.oi_major && !p.split;
+    bool oi_major;
+    float* gz = wg_store_base(p, gw, ws, z, b, oi_major);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int ic = i0 + wn * 64 + j * 32 + lr;
-            if (ic >= p.ldgw) continue;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int o = o0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                if (o >= p.O) continue;
-                float* dst = oi_major ? gz + ((long long)o * p.I + ic) * taps + tap
-                                      : gz + ((long long)o * taps + tap) * p.ldgw + ic;
-                if (oi_major && ic >= p.I) continue;
-                *dst = acc[i][j][e] * p.gain;
-            }
+            for (int e = 0; e < 16; ++e)
+                wg_store(p, gz, oi_major, o0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh, ic, tap, taps, acc[i][j][e]);
         }
 }
 
@@ -597,27 +530,24 @@ static bool conv_wgrad_generic_eligible(const WgradProblem& q, WgradPlan* plan) 
 static void conv_wgrad_generic_launch(const WgradProblem& q, const WgradPlan& plan, const void* gy, const void* x, float* gw,
                                       float* ws, void* stream) {
     WgradParams p{};
-    p.B = q.B; p.IH = q.IH; p.IW = q.IW; p.Cx = q.Cx; p.I = q.I; p.OH = q.OH; p.OW = q.OW; p.ldgy = q.ldgy; p.O = q.O;
+    wgrad_fill_common(p, q, plan);
+    p.IH = q.IH; p.IW = q.IW; p.OH = q.OH; p.OW = q.OW;
     p.kh = q.kh; p.kw = q.kw; p.stride = q.stride; p.pad = q.pad; p.pixel_shuffle = q.pixel_shuffle;
-    p.per_sample = q.per_sample; p.ldgw = q.ldgw; p.oi_major = q.oi_major; p.gain = q.gain;
-    p.o_tiles = (q.O + WT - 1) / WT; p.i_tiles = (q.I + WT - 1) / WT; p.gw_zstride = q.gw_zstride(); p.slab = q.slab();
-    p.OWv = plan.OWv; p.OHv = plan.OHv; p.pix_per_chunk = plan.slice_pixels; p.nz = plan.nz; p.fold = plan.fold;
-    p.chunks_per_sample = plan.fold ? plan.nz : q.k_chunks; p.split = plan.chunks_per_out > 1; p.xcd_slices = plan.xcd_slices;
+    p.OWv = plan.OWv; p.OHv = plan.OHv; p.pix_per_chunk = plan.slice_pixels; p.fold = plan.fold;
+    p.chunks_per_sample = plan.fold ? plan.nz : q.k_chunks; p.xcd_slices = plan.xcd_slices;
     const dim3 grid((unsigned)plan.blocks);
-    hipStream_t s = (hipStream_t)stream;
-    const bool dma = plan.kernel == WGRAD_DMA, uni = plan.kernel == WGRAD_UNI;
-    if (q.dtype == MSG_BF16) {
-        if (dma) hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, true, false>), grid, dim3(256), 0, s, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
-        else if (uni) hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, false, true>), grid, dim3(256), 0, s, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, false, false>), grid, dim3(256), 0, s, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
-    } else if (q.split == 3) {
-        if (uni) hipLaunchKernelGGL((conv_wgrad_kernel<float, false, true, 3>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<float, false, false, 3>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
-    } else {
-        if (dma) hipLaunchKernelGGL((conv_wgrad_kernel<float, true, false>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
-        else if (uni) hipLaunchKernelGGL((conv_wgrad_kernel<float, false, true>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<float, false, false>), grid, dim3(256), 0, s, (const float*)gy, (const float*)x, gw, ws, p);
-    }
+#define WGRAD(T, ...) hipLaunchKernelGGL((conv_wgrad_kernel<T, __VA_ARGS__>), grid, dim3(256), 0, (hipStream_t)stream, \
+                                         (const T*)gy, (const T*)x, gw, ws, p)
+    const bool bf16 = q.dtype == MSG_BF16, dma = plan.kernel == WGRAD_DMA, uni = plan.kernel == WGRAD_UNI;
+    if (bf16 && dma) WGRAD(bf16_t, true, false);
+    else if (bf16 && uni) WGRAD(bf16_t, false, true);
+    else if (bf16) WGRAD(bf16_t, false, false);
+    else if (q.split == 3 && uni) WGRAD(float, false, true, 3);
+    else if (q.split == 3) WGRAD(float, false, false, 3);
+    else if (dma) WGRAD(float, true, false);
+    else if (uni) WGRAD(float, false, true);
+    else WGRAD(float, false, false);
+#undef WGRAD
 }
 
 // The only place that knows the order of the weight-gradient kernels.

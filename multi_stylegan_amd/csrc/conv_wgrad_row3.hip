@@ -12,18 +12,13 @@
 // (the GY fragments are shared by the three taps).  Three accumulator sets (3 x 64 registers) mean one workgroup of four
 // waves per CU, in the unified VGPR/AGPR file -- the one-wave-per-SIMD regime, with a third of its staging per MFMA.
 //
-// Same LDS image as conv_wgrad.hip ([pixel][128 channels], rows rotated by 64 B * (pixel & 3), ds_read_b64_tr_b16),
-// same buffer-load addressing (per-thread constant offset + wave-uniform SGPR cursor, out-of-range rows read zeros),
-// same fp32 epilogue (plain stores into GW[o][tap][i], or into the K-slice's slab when the sum is split: conv_wgrad.hip).
-#include "conv_dispatch.h"
+// Same LDS image as conv_wgrad.hip ([pixel][128 channels], rows rotated by 64 B * (pixel & 3), ds_read_b64_tr_b16) and same
+// fp32 store (plain stores into GW[o][tap][i], or into the K-slice's slab when the sum is split): both in conv_wgrad_tile.h.
+// Same buffer-load addressing (per-thread constant offset + wave-uniform SGPR cursor, out-of-range rows read zeros).
+#include "conv_wgrad_tile.h"
 #include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
-
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char* r3_lds_t;
 
 struct Row3Params {
     int B, H, W, Cx, I, ldgy, O, ldgw;
@@ -39,7 +34,6 @@ constexpr int R3_KP = 64;                             // pixels per K-step
 constexpr int R3_TA = R3_KP * R3_ROW;                 // 16 KiB: GY segment
 constexpr int R3_TB = (R3_KP + 4) * R3_ROW;           // 17 KiB: X segment + neighbours (66 rows used)
 constexpr int R3_STAGE = R3_TA + R3_TB;
-constexpr int R3_OOB = (int)0x80000000;
 
 // W32: the map is exactly 32 pixels wide -- a K-step is TWO whole image rows; each occupies 34 rows of the X tile (its 32
 // pixels between two zero rows: lanes whose source is out of range), tap kw of pixel p of image row q reads X row 34 q + p + kw.
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
     // ---- staging: piece j of wave w is the 1-KiB chunk c = w + 4 j of an operand's tile (rows 4 c .. 4 c + 3); the X tile
     // has a 17th chunk (rows 64..67: the right neighbour and spare rows), piece 4 of wave 0.  X row r' holds image column
     // col - 1 + r' (W32: image row q = r' / 34 between two zero rows, pixel 32 q + r' % 34 - 1).
-    const int lrow = lane >> 4, chl = ((lane & 15) - 4 * lrow) & 15;      // row inside the chunk (= row & 3), logical channel chunk
+    const int lrow = lane >> 4, chl = wg_dma_chunk<R3_ROW>(lrow, lane & 15);   // row inside the chunk (= row & 3), logical channel chunk
     const int oc = o0 + chl * 8, ic = i0 + chl * 8;
     const bool oc_ok = oc + 8 <= p.ldgy, ic_ok = ic + 8 <= p.Cx;
     const int u_L = p.ldgy * 2, u_C = p.Cx * 2;
@@ -133,30 +127,30 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int r = 4 * (wid_u + 4 * j) + lrow;
-        voff_gy[j] = oc_ok ? r * u_L + oc * 2 : R3_OOB;
+        voff_gy[j] = oc_ok ? r * u_L + oc * 2 : MSG_DMA_OOB;
     }
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         const int r = 4 * (j < 4 ? wid_u + 4 * j : 16) + lrow;
         if constexpr (!W32) {
-            voff_x[j] = (ic_ok && r < R3_KP + 2) ? r * u_C + ic * 2 : R3_OOB;
+            voff_x[j] = (ic_ok && r < R3_KP + 2) ? r * u_C + ic * 2 : MSG_DMA_OOB;
             x_q1[j] = false;
         } else {
             const int qq = r >= 34 ? 1 : 0, pos = r - 34 * qq;
-            voff_x[j] = (ic_ok && pos >= 1 && pos <= 32) ? (32 * qq + pos - 1) * u_C + ic * 2 : R3_OOB;
+            voff_x[j] = (ic_ok && pos >= 1 && pos <= 32) ? (32 * qq + pos - 1) * u_C + ic * 2 : MSG_DMA_OOB;
             x_q1[j] = qq != 0;
         }
     }
     // (columns outside the map: X row 0 of a row's first segment -- column -1 -- and X row 65 of its last one)
-    const int voff_x0_left = (wid_u == 0 && lrow == 0) ? R3_OOB : voff_x[0];
-    const int voff_x4_right = lrow == 1 ? R3_OOB : voff_x[4];
+    const int voff_x0_left = (wid_u == 0 && lrow == 0) ? MSG_DMA_OOB : voff_x[0];
+    const int voff_x4_right = lrow == 1 ? MSG_DMA_OOB : voff_x[4];
     const long long sample_gy = (long long)p.H * p.W * u_L, sample_x = (long long)p.H * p.W * u_C;
     const char* gbase = (const char*)gy + (p.per_sample ? (long long)b * sample_gy : 0);
     const char* xbase = (const char*)x + (p.per_sample ? (long long)b * sample_x : 0) +
                         ((long long)(khi - p.pad) * p.W - (W32 ? 0 : 1)) * u_C;
     // (descriptors as four SGPRs for the inline-assembly DMA below: base, no stride, 2^31 records, raw dword format)
     const msg_desc_t d_gy = msg_make_desc(gbase), d_x = msg_make_desc(xbase);
-    const unsigned lds0 = (unsigned)(unsigned long long)(r3_lds_t)smem;
+    const unsigned lds0 = (unsigned)(unsigned long long)(lds_t)smem;
 
     f32x4 acc[3][4][4];
 #pragma unroll
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
     auto dma_piece = [&](int q, int stage, bool live) __attribute__((always_inline)) {
 #if defined(__HIP_DEVICE_COMPILE__)
         if (q < 4) {
-            msg_dma16(d_gy, lds0 + stage * R3_STAGE + (wid_u + 4 * q) * 1024, live ? voff_gy[q] : R3_OOB, so_gy);
+            msg_dma16(d_gy, lds0 + stage * R3_STAGE + (wid_u + 4 * q) * 1024, live ? voff_gy[q] : MSG_DMA_OOB, so_gy);
         } else {
             const int j = q - 4;
             if (j == 4 && wid_u != 0) return;
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
             if (!W32 && j == 0) off = col_l == 0 ? voff_x0_left : off;
             if (!W32 && j == 4) off = col_l + R3_KP == p.W ? voff_x4_right : off;
             const bool ok = live & (W32 ? (x_q1[j] ? row_ok1 : row_ok) : row_ok);
-            msg_dma16(d_x, la, ok ? off : R3_OOB, so_x);
+            msg_dma16(d_x, la, ok ? off : MSG_DMA_OOB, so_x);
         }
 #endif
     };
@@ -222,21 +216,17 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
     int cA[4], cB[NPAR][3][4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        cA[t] = (8 * g4 + q) * R3_ROW + ((((wm * 64 + t * 16 + 4 * pq) * 2) + ((q & 3) << 6)) & (R3_ROW - 1));
+        cA[t] = wg_image_off<R3_ROW>(8 * g4 + q, (wm * 64 + t * 16 + 4 * pq) * 2);
 #pragma unroll
         for (int par = 0; par < NPAR; ++par)
 #pragma unroll
             for (int k = 0; k < 3; ++k)
-                cB[par][k][t] = R3_TA + (8 * g4 + q) * R3_ROW +
-                                ((((wn * 64 + t * 16 + 4 * pq) * 2) + (((q + k + 2 * par) & 3) << 6)) & (R3_ROW - 1));
+                // (the image offset of the row the lane addresses, less the shift's rows: they are part of `rows` at the read)
+                cB[par][k][t] = R3_TA + wg_image_off<R3_ROW>(8 * g4 + q + k + 2 * par, (wn * 64 + t * 16 + 4 * pq) * 2) -
+                                (k + 2 * par) * R3_ROW;
     }
     auto frag = [&](const char* stage_base, int c, int rows) __attribute__((always_inline)) {
-        s16x4 part[2];
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-            part[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (s16x4 __attribute__((address_space(3)))*)(stage_base + c + (rows + 4 * half) * R3_ROW));
-        return __builtin_bit_cast(bf16v8, (s16x8)__builtin_shufflevector(part[0], part[1], 0, 1, 2, 3, 4, 5, 6, 7));
+        return wg_frag_read(stage_base + c + rows * R3_ROW, 4 * R3_ROW);
     };
     bf16v8 fa[2][4], fb[2][3][4];
     auto read_nth = [&](int f, int s, const char* base) __attribute__((always_inline)) {
@@ -313,8 +303,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
     // ---- epilogue: fp32; lanes 0..15 of a row group = 16 consecutive input channels, one pass per tap and block
     const int l15 = lane & 15;
     const int taps = p.kh * 3;
-    float* gz = p.split ? ws + (long long)z * p.slab : gw + (p.per_sample ? (long long)b * p.gw_zstride : 0);
-    const bool oi_major = p.oi_major && !p.split;
+    bool oi_major;
+    float* gz = wg_store_base(p, gw, ws, z, b, oi_major);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const int tap = khi * 3 + k;
@@ -323,16 +313,9 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_row3s_kernel(const bf16_t* 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int icn = i0 + wn * 64 + j * 16 + l15;
-                if (icn >= p.ldgw) continue;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int o = o0 + wm * 64 + i * 16 + 4 * g4 + e;
-                    if (o >= p.O) continue;
-                    float* dst = oi_major ? gz + ((long long)o * p.I + icn) * taps + tap
-                                          : gz + ((long long)o * taps + tap) * p.ldgw + icn;
-                    if (oi_major && icn >= p.I) continue;
-                    *dst = acc[k][i][j][e] * p.gain;
-                }
+                for (int e = 0; e < 4; ++e)
+                    wg_store(p, gz, oi_major, o0 + wm * 64 + i * 16 + 4 * g4 + e, icn, tap, taps, acc[k][i][j][e]);
             }
     }
 }
@@ -388,10 +371,9 @@ bool conv_wgrad_row3_eligible(const WgradProblem& q, WgradPlan* plan) {
 void conv_wgrad_row3_launch(const WgradProblem& q, const WgradPlan& plan, const void* gy, const void* x, float* gw, float* ws,
                             void* stream) {
     Row3Params p{};
-    p.B = q.B; p.H = q.OH; p.W = q.OW; p.Cx = q.Cx; p.I = q.I; p.ldgy = q.ldgy; p.O = q.O; p.ldgw = q.ldgw;
-    p.kh = q.kh; p.pad = q.pad; p.per_sample = q.per_sample; p.oi_major = q.oi_major; p.gain = q.gain;
-    p.o_tiles = (q.O + 127) / 128; p.i_tiles = (q.I + 127) / 128; p.gw_zstride = q.gw_zstride(); p.slab = q.slab();
-    p.steps_per_chunk = plan.slice_pixels / R3_KP; p.chunks_per_sample = plan.chunks_per_out; p.nz = plan.nz; p.split = plan.chunks_per_out > 1;
+    wgrad_fill_common(p, q, plan);
+    p.H = q.OH; p.W = q.OW; p.kh = q.kh; p.pad = q.pad;
+    p.steps_per_chunk = plan.slice_pixels / R3_KP; p.chunks_per_sample = plan.chunks_per_out;
     auto* kernel = plan.kernel == WGRAD_ROW3_W32 ? conv_wgrad_row3s_kernel<true> : conv_wgrad_row3s_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)plan.blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gy, (const bf16_t*)x, gw, ws, p);
 }

@@ -23,6 +23,14 @@ typedef short  bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;
 typedef _Float16 f16_t;            // IEEE half storage (the reference's `half` dispatch): FIR / activation entries only
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16-B staging register (plain vector: stays in VGPRs)
+typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));        // bf16 MFMA operand
+typedef short s16x4 __attribute__((ext_vector_type(4)));          // what a transposing LDS read returns; two of them make an operand
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+// explicit address spaces: loads through a global pointer are global_load (never flat_load, which would force a vmcnt(0) in
+// front of every LDS access and serialise the pipeline); an LDS pointer is what the LDS-DMA builtins and addresses take
+typedef const __attribute__((address_space(1))) char* gptr_t;
+typedef const __attribute__((address_space(1))) u32x4* gvec_t;
+typedef __attribute__((address_space(3))) char* lds_t;
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
@@ -234,6 +242,28 @@ __device__ __forceinline__ void msg_dma16(msg_desc_t desc, unsigned lds_addr, in
 #endif
 }
 #pragma clang diagnostic pop
+
+// MSG_F32_SPLIT staging (conv_fprop.hip, conv_wgrad.hip): the four floats of a staged 16-byte vector -> SPLIT planes of four bf16
+// (hi = RNE(x), mid = RNE(x - hi), lo = RNE(x - hi - mid)), 8 bytes per plane, plane p parked at dst + p * plane_bytes.
+template <int SPLIT>
+__device__ __forceinline__ void msg_split_park(const u32x4& raw, char* dst, int plane_bytes) {
+    uint2 pl[3];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float x0 = __uint_as_float(raw[2 * h]), x1 = __uint_as_float(raw[2 * h + 1]);
+        const unsigned hp = (unsigned)f2bf(x0) | ((unsigned)f2bf(x1) << 16);
+        const float r0 = x0 - __uint_as_float(hp << 16), r1 = x1 - __uint_as_float(hp & 0xffff0000u);
+        const unsigned mp = (unsigned)f2bf(r0) | ((unsigned)f2bf(r1) << 16);
+        (h ? pl[0].y : pl[0].x) = hp;
+        (h ? pl[1].y : pl[1].x) = mp;
+        if constexpr (SPLIT == 3) {
+            const float q0 = r0 - __uint_as_float(mp << 16), q1 = r1 - __uint_as_float(mp & 0xffff0000u);
+            (h ? pl[2].y : pl[2].x) = (unsigned)f2bf(q0) | ((unsigned)f2bf(q1) << 16);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < SPLIT; ++p) *reinterpret_cast<uint2*>(dst + p * plane_bytes) = pl[p];
+}
 
 #define MSG_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? MSG_OK : MSG_ELAUNCH)
 

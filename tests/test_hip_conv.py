@@ -212,6 +212,76 @@ def test_weight_gradient_plan_branches(case):
     assert rel_err(gw, gw_r) < TOLS[dtype], (name, rel_err(gw, gw_r))
 
 
+STORE_EDGES = [  # name, storage, contraction mode, H, W, k, per-sample, what the plan must say
+    ("row3_direct", torch.bfloat16, None, 4, 64, 3, False, dict(kernel="ROW3", need=0)),
+    ("row3_split", torch.bfloat16, None, 8, 64, 3, False, dict(kernel="ROW3", chunks_per_out=4)),
+    ("row3_per_sample", torch.bfloat16, None, 4, 64, 3, True, dict(kernel="ROW3", n_out=2, need=0)),
+    ("row3_per_sample_split", torch.bfloat16, None, 32, 64, 3, True, dict(kernel="ROW3", chunks_per_out=2)),
+    ("w32_direct", torch.bfloat16, None, 4, 32, 3, False, dict(kernel="ROW3_W32", need=0)),
+    ("uni_direct", torch.bfloat16, None, 8, 8, 3, False, dict(kernel="UNI", need=0)),
+    ("generic_direct", torch.bfloat16, None, 12, 24, 3, False, dict(kernel="GENERIC", need=0)),
+    ("uni_split_xcd", torch.bfloat16, None, 32, 32, 1, False, dict(kernel="UNI", chunks_per_out=8, xcd_slices=1)),
+    ("fp32_exact", torch.float32, "exact", 8, 8, 3, False, dict(kernel="UNI", need=0)),
+    ("split_bf16x3", torch.float32, "split_bf16x3", 8, 8, 3, False, dict(kernel="UNI", need=0)),
+]
+
+
+@pytest.mark.parametrize("case", STORE_EDGES, ids=[c[0] for c in STORE_EDGES])
+def test_weight_gradient_store_edges(case):
+    """The stores of the weight-gradient kernels where their guards matter, built like test_weight_gradient_plan_branches (same
+    float64 reference, same tolerances, the plan asserted through msg_conv2d_wgrad_plan): B = 2, O = 136 -- two output-channel
+    tiles, the second with 8 rows -- I = 70 on a channel stride of 72 = ldgw, gain 0.5.
+    (a) kernel layout [(B)][O][tap][ldgw]: the values, exact zeros in the padding columns I .. ldgw - 1, no NaN left;
+    (b) shared weights, the parameter's own [O, I, kh, kw] layout written into a slice of a NaN-filled buffer: the values, and
+    every guard float on both sides still NaN.  Without a split that is the contraction kernel's own oi_major store (guard
+    ic >= I included), with one the reduce's."""
+    import ctypes
+    from multi_stylegan_amd import _lib, conv_ops
+    name, dtype, mode, h, w_, k, per_sample, expect = case
+    b, o, i, gain = 2, 136, 70, 0.5
+    cx = ldgw = 72
+    pad = k // 2
+    g = torch.Generator().manual_seed(len(name) * 19)
+    x = torch.randn(b, i, h, w_, generator=g).to(dtype)
+    gy = torch.randn(b, o, h, w_, generator=g).to(dtype)
+    code = {None: _lib.MSG_BF16, "exact": _lib.MSG_F32, "split_bf16x3": _lib.MSG_F32_SPLIT}[mode]
+    geom = (code, b, h, w_, cx, i, h, w_, o, o, ldgw, k, k, 1, pad, 0, int(per_sample), _lib.MSG_WGRAD_K_AUTO)
+    out = (ctypes.c_longlong * _lib.MSG_WPLAN_FIELDS)()
+    assert _lib.lib().msg_conv2d_wgrad_plan(*geom, ctypes.addressof(out), len(out)) == _lib.MSG_OK
+    plan = dict(zip(("kernel", "nz", "chunks_per_out", "n_out", "slice_pixels", "OWv", "OHv", "fold", "xcd_slices", "blocks", "need"), out))
+    want = dict(expect, kernel=getattr(_lib, "MSG_WPLAN_" + expect["kernel"]))
+    assert {key: plan[key] for key in want} == want, plan
+
+    ref = lambda xb, gb: torch.nn.grad.conv2d_weight(xb, (o, i, k, k), gb, padding=pad)      # float64, one weight set
+    xr, gr = x.double(), gy.double()
+    gw_r = gain * (torch.stack([ref(xr[n:n + 1], gr[n:n + 1]) for n in range(b)]) if per_sample else ref(xr, gr))
+    cl = lambda t: t.to(DEV).contiguous(memory_format=torch.channels_last)
+    xd, gd = cl(x), cl(gy)
+
+    raw, ld = conv_ops._launch_wgrad(gd, xd, o, i, k, k, 1, pad, False, per_sample, None, raw=True, gain=gain, mode=mode)
+    lead = (b, o) if per_sample else (o,)
+    assert ld == ldgw and raw.shape == (*lead, k * k, ldgw)
+    assert not torch.isnan(raw).any()
+    want_raw = gw_r.reshape(*lead, i, k * k).transpose(-1, -2)                                 # [(B)][O][tap][I]
+    err = rel_err(raw[..., :i], want_raw)
+    print(name, "kernel layout", err)
+    assert err < TOLS[dtype], (name, err)
+    assert torch.count_nonzero(raw[..., i:]) == 0, "padding columns I .. ldgw - 1"
+    if per_sample:
+        return
+
+    n, guard = o * i * k * k, 64
+    buf = torch.full((guard + n + guard,), float("nan"), dtype=torch.float32, device=DEV)
+    dst = buf[guard:guard + n]
+    assert dst.data_ptr() % 16 == 0
+    gw = conv_ops._launch_wgrad(gd, xd, o, i, k, k, 1, pad, False, False, None, gain=gain, out=dst, mode=mode)
+    assert gw.shape == gw_r.shape and gw.data_ptr() == dst.data_ptr()
+    err = rel_err(gw, gw_r)
+    print(name, "parameter layout", err)
+    assert err < TOLS[dtype], (name, err)
+    assert torch.isnan(buf[:guard]).all() and torch.isnan(buf[guard + n:]).all(), "guard floats around the parameter-layout result"
+
+
 @pytest.mark.parametrize("case", PLAN_BRANCHES, ids=[c[0] for c in PLAN_BRANCHES])
 def test_weight_gradient_auto_split_runs_the_rules_plan(case):
     """msg_conv2d_wgrad with k_chunks = MSG_WGRAD_K_AUTO against the same call with the number the Python layer used to pass
