@@ -880,6 +880,50 @@ int msg_metric_input(const void* images, int in_dtype, int B, int C, int T, int 
                      int channel, int t, void* out, int out_dtype, int planes,
                      int out_h, int out_w, int norm, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Pairwise feature kernels: what the sample-based validation metrics (validation_metrics.py: KID / KVD, manifold precision /
+ * recall / density / coverage) need of two sets of feature rows -- every pair (q_i, r_j), reduced where it is formed.  The
+ * nq x nr matrix is never written; the reference has no such metric (its FID / FVD keep moments only).
+ * Feature sets are fp32 [n, d], contiguous, 4-byte aligned (16-byte aligned sets with d % 4 == 0 are read 16 bytes per lane,
+ * anything else element by element, with the same bits), d >= 1, all values finite (the caller's duty: max(0, .) and the
+ * comparisons drop a NaN silently).  Row offsets are 64-bit.
+ * Arithmetic: q . r is the exact-fp32 matrix instruction (one fmaf chain in ascending k per pair, the same bits for (a, b) and
+ * (b, a)); |x|^2 likewise one fmaf chain per row; dist2(q, r) = max(0, (|q|^2 + |r|^2) - 2 q . r) in fp32.  Its error grows with
+ * the norms, not with the distance: callers centre their sets first (validation_metrics.manifold_scores does).
+ * One launch sweeps the pairs on a (query tile, sweep slice[, product]) grid and leaves per-slice results in ws; a second, small
+ * launch merges the slices in slice order.  ws: the entry's _workspace(...) BYTES, needs no initialisation, carries nothing
+ * between calls.  No atomics; every output is bit-identical from run to run.
+ * MSG_EINVAL (all three): a NULL pointer where none is allowed, a non-positive size, a misaligned pointer (4 bytes; 8 for the
+ * float64 sums and their ws).  Nothing is launched and no output byte is written on refusal; the _workspace queries return -1
+ * for sizes the entry refuses.
+ *
+ * msg_feature_knn   out[i] (fp32 [nq]) = the k-th smallest dist2(q_i, r_j) over j, 1 <= k <= MSG_FEATURE_KNN_MAX.
+ *   exclude_self != 0 (legal only with q == r and nq == nr, else MSG_EINVAL): j = i is skipped BY INDEX -- a duplicate of row i
+ *   elsewhere in the set is a genuine neighbour at distance 0.  MSG_EINVAL if k exceeds the rows available (nr, less one with
+ *   exclude_self).  Uses: manifold radii (q = r, exclude_self, k = 3 or 5); nearest cross-set distance (k = 1).
+ * msg_feature_ball_hits   radius2 fp32 [nr], >= 0.  margin[i] (fp32 [nq]) = min_j (dist2(q_i, r_j) - radius2[j]);
+ *   count[i] (int32 [nq]) = #{j : dist2(q_i, r_j) <= radius2[j]}.  Either output may be NULL (both: MSG_EINVAL).  margin <= 0
+ *   is "inside the union of balls"; its size says how near a tie the decision was.  Uses: precision, recall, density.
+ * msg_poly_mmd   the three kernel sums of the polynomial-kernel MMD^2 (KID), for S subsets in one call.
+ *   x [nx, d], y [ny, d]; ix int32 [S, mx], iy int32 [S, my]: row indices into x / y, gathered while staging (no gathered copy is
+ *   written).  Either may be NULL: the identity 0 .. n - 1, and then m must equal n (else MSG_EINVAL).  The indices live on
+ *   the device and are not checked by the entry: an index in [0, n) is the caller's duty; one outside it reads as a row of zeros.
+ *   k(u, v) = (gamma u . v + coef0)^3 in fp32, the cube as two multiplies; every value is widened to float64 before it is added.
+ *   sums float64 [S, 3]: sum_{a != b} k(x_a, x_b), sum_{a != b} k(y_a, y_b), sum_{a, b} k(x_a, y_b), a and b positions in the
+ *   subset's lists (a row listed twice is two positions).  The two symmetric sums visit the upper triangle of tiles and double
+ *   it.  MSG_EINVAL also for 3 S > 65535 (what a block index addresses).
+ * ------------------------------------------------------------------------- */
+#define MSG_FEATURE_KNN_MAX 8
+long long msg_feature_knn_workspace(int nq, int nr, int d, int k, int exclude_self);
+int msg_feature_knn(const float* q, int nq, const float* r, int nr, int d, int k, int exclude_self, float* out,
+                    void* ws, void* stream);
+long long msg_feature_ball_hits_workspace(int nq, int nr, int d);
+int msg_feature_ball_hits(const float* q, int nq, const float* r, int nr, int d, const float* radius2, float* margin,
+                          int* count, void* ws, void* stream);
+long long msg_poly_mmd_workspace(int nx, int ny, int d, int S, int mx, int my);
+int msg_poly_mmd(const float* x, int nx, const float* y, int ny, int d, const int* ix, const int* iy, int S, int mx, int my,
+                 float gamma, float coef0, double* sums, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

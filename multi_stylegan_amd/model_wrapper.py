@@ -390,7 +390,8 @@ class ModelWrapper(object):
     def validation(self, training_dataset) -> Dict[str, float]:
         """The reference's ``validation`` (model_wrapper.py:197-243): every metric of ``validation_metrics`` on the EMA
         generator and the training data, scores logged as ``<Class>_bf`` / ``_gfp`` / ``_rfp`` (returned, and kept in the
-        wrapper's log), the best bright-field FVD remembered."""
+        wrapper's log), the best bright-field FVD remembered.  A metric whose score is a ``NamedTuple``
+        (``PrecisionRecall``: a ``ManifoldScores``) is logged field by field, ``<Class>_<field>_bf`` / ``_gfp`` / ``_rfp``."""
         self.generator_ema.eval()
         scores_out: Dict[str, float] = {}
         for metric in self.validation_metrics:
@@ -398,8 +399,14 @@ class ModelWrapper(object):
             name = metric.__class__.__name__
             if isinstance(scores, (int, float)):
                 scores = (float(scores),)
+            elif hasattr(scores, "_fields"):                     # one channel's NamedTuple (e.g. ManifoldScores), not a tuple of channels
+                scores = (scores,)
             for suffix, value in zip(("_bf", "_gfp", "_rfp"), scores):
-                scores_out[name + suffix] = float(value)
+                if hasattr(value, "_fields"):                    # logged field by field: <Class>_<field>_bf
+                    for field in value._fields:
+                        scores_out[f"{name}_{field}{suffix}"] = float(getattr(value, field))
+                else:
+                    scores_out[name + suffix] = float(value)
             if "FVD" in name and self.best_fvd > scores[0]:
                 self.best_fvd = float(scores[0])
         self._record(**{k: torch.tensor(v, device=self.device) for k, v in scores_out.items()})

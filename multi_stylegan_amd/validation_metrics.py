@@ -19,7 +19,7 @@ eigenvalues clamped at zero where scipy's ``sqrtm(...).real`` drops an imaginary
 import functools
 import math
 import warnings
-from typing import Iterable, Optional, Tuple, Union
+from typing import Iterable, NamedTuple, Optional, Tuple, Union
 
 import torch
 import torch.distributed as torch_dist
@@ -35,7 +35,8 @@ def _ranks() -> int:
     return torch_dist.get_world_size() if torch_dist.is_available() and torch_dist.is_initialized() else 1
 
 __all__ = ["IS", "FID", "FVD", "FeatureMoments", "frechet_distance", "frechet_distance_from_moments", "inception_score",
-           "metric_inputs", "select_frames"]
+           "metric_inputs", "select_frames", "KID", "KVD", "PrecisionRecall", "PrecisionRecallVideo", "FeatureRows",
+           "ManifoldScores", "kernel_distance", "manifold_scores", "subset_indices"]
 
 
 def select_frames(images: torch.Tensor, channel: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -348,3 +349,332 @@ class FVD(_Frechet):
 
     def _inputs(self, images, channel):
         return metric_inputs(images, channel, t=None, size=self.input_size, normalize="source")
+
+
+# ------------------------------------------------------------------------------------------------- sample-based metrics
+# KID / KVD and manifold precision / recall / density / coverage ("Sample-based metrics").  They need the
+# feature ROWS, not their moments; on the GPU every pair of rows is formed and reduced by csrc/feature_pairs.hip
+# (msg_feature_knn, msg_feature_ball_hits, msg_poly_mmd) and no [N, M] array is written.  CPU tensors take the host statement
+# of the same definitions in float64 (``_host_*`` below), as ``metric_inputs`` does.
+class FeatureRows:
+    """The sample-keeping sibling of ``FeatureMoments``: the feature rows themselves, fp32 on the features' device, ``limit``
+    rows at most."""
+
+    def __init__(self, limit: Optional[int] = None):
+        self.limit, self.n = limit, 0
+        self._parts: list = []
+
+    @property
+    def full(self) -> bool:
+        return self.limit is not None and self.n >= self.limit
+
+    def update(self, features: torch.Tensor) -> "FeatureRows":
+        f = features.detach().flatten(start_dim=1).to(torch.float32)
+        if self.limit is not None:
+            f = f[:max(0, self.limit - self.n)]
+        if f.shape[0] == 0:
+            return self
+        if self._parts and self._parts[0].shape[1] != f.shape[1]:
+            raise ValueError(f"feature rows of width {f.shape[1]} after rows of width {self._parts[0].shape[1]}")
+        self._parts.append(f.clone() if f.data_ptr() == features.data_ptr() else f)      # (never a view of the network's output)
+        self.n += f.shape[0]
+        return self
+
+    @property
+    def rows(self) -> torch.Tensor:
+        """One contiguous fp32 ``[n, d]`` tensor.  A row that is not finite raises: the kernels' comparisons would drop it
+        silently."""
+        if not self._parts:
+            raise ValueError("no feature rows were collected")
+        if len(self._parts) > 1:
+            self._parts = [torch.cat(self._parts)]
+        rows = self._parts[0].contiguous()
+        if not bool(torch.isfinite(rows).all()):
+            bad = (~torch.isfinite(rows).all(dim=1)).nonzero().flatten()[:8].tolist()
+            raise ValueError(f"feature rows {bad} hold values that are not finite")
+        return rows
+
+    def all_gather_(self) -> "FeatureRows":
+        """Every rank ends with the rows of all ranks, in rank order (the exchange ``IS.__call__`` makes for its probabilities).
+        The ranks' shares are equal by construction (``share = ceil(data_samples / ranks)`` rows each); unequal ones raise."""
+        if _ranks() > 1:
+            if not self._parts:
+                raise ValueError("a rank without feature rows cannot join the exchange (its feature width is unknown)")
+            mine = self.rows
+            counts = [torch.zeros(1, dtype=torch.int64, device=mine.device) for _ in range(_ranks())]
+            torch_dist.all_gather(counts, torch.tensor([mine.shape[0]], dtype=torch.int64, device=mine.device))
+            if len({int(c) for c in counts}) != 1:
+                raise ValueError(f"the ranks hold unequal shares of feature rows: {[int(c) for c in counts]}")
+            parts = [torch.empty_like(mine) for _ in range(_ranks())]
+            torch_dist.all_gather(parts, mine)
+            self._parts, self.n = [torch.cat(parts)], sum(p.shape[0] for p in parts)
+        return self
+
+
+class ManifoldScores(NamedTuple):
+    precision: float
+    recall: float
+    density: float
+    coverage: float
+
+
+def _feature_sets(*sets: torch.Tensor):
+    """``[n, d]`` feature sets of one width on one device -> (on the GPU?, the sets: fp32 contiguous there, float64 on the host)."""
+    sets = tuple(torch.as_tensor(s).detach() for s in sets)
+    for s in sets:
+        if s.ndim != 2 or s.shape[0] < 1 or s.shape[1] < 1:
+            raise ValueError(f"expected [n, d] feature rows, got {tuple(s.shape)}")
+        if s.shape[1] != sets[0].shape[1] or s.device != sets[0].device:
+            raise ValueError("the feature sets differ in width or device")
+    if sets[0].is_cuda:
+        return True, tuple(s.to(torch.float32).contiguous() for s in sets)
+    return False, tuple(s.to(torch.float64) for s in sets)
+
+
+def _host_dist2(q: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """float64 ``[nq, nr]`` squared distances as sums of squared differences, a block of query rows at a time."""
+    step = max(1, (1 << 24) // max(1, r.shape[0] * r.shape[1]))
+    return torch.cat([(q[i:i + step, None, :] - r[None, :, :]).square().sum(dim=2) for i in range(0, q.shape[0], step)])
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    if nbytes < 0:
+        raise _lib.MsgHipError("the feature-pair kernels refuse these sizes")
+    return torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+
+
+def _knn(q: torch.Tensor, r: torch.Tensor, k: int, exclude_self: bool, gpu: bool) -> torch.Tensor:
+    """The k-th smallest squared distance from every row of ``q`` to the rows of ``r`` (``exclude_self``: ``q is r``, row i
+    skipped by index)."""
+    if gpu:
+        dev = _lib.require_gpu(q, r)
+        (nq, d), nr, lib = q.shape, r.shape[0], _lib.lib()
+        out = torch.empty(nq, dtype=torch.float32, device=dev)
+        ws = _workspace(lib.msg_feature_knn_workspace(nq, nr, d, k, int(exclude_self)), dev)
+        with _lib.on_device(dev):
+            with _lib.kernel_clock.span(("feature_knn", k), 2.0 * nq * nr * d):
+                _lib.check(lib.msg_feature_knn(q.data_ptr(), nq, r.data_ptr(), nr, d, k, int(exclude_self), out.data_ptr(),
+                                               ws.data_ptr(), _lib.stream_of(dev)), "msg_feature_knn")
+        return out
+    dist = _host_dist2(q, r)
+    if exclude_self:
+        dist = dist.clone()
+        dist.fill_diagonal_(math.inf)
+    return dist.kthvalue(k, dim=1).values
+
+
+def _ball_hits(q: torch.Tensor, r: torch.Tensor, radius2: torch.Tensor, gpu: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(min_j (dist2(q_i, r_j) - radius2[j]), #{j: dist2(q_i, r_j) <= radius2[j]}) for every row of ``q``."""
+    if gpu:
+        dev = _lib.require_gpu(q, r, radius2)
+        (nq, d), nr, lib = q.shape, r.shape[0], _lib.lib()
+        radius2 = radius2.to(torch.float32).contiguous()
+        margin = torch.empty(nq, dtype=torch.float32, device=dev)
+        count = torch.empty(nq, dtype=torch.int32, device=dev)
+        ws = _workspace(lib.msg_feature_ball_hits_workspace(nq, nr, d), dev)
+        with _lib.on_device(dev):
+            with _lib.kernel_clock.span(("feature_ball_hits",), 2.0 * nq * nr * d):
+                _lib.check(lib.msg_feature_ball_hits(q.data_ptr(), nq, r.data_ptr(), nr, d, radius2.data_ptr(), margin.data_ptr(),
+                                                     count.data_ptr(), ws.data_ptr(), _lib.stream_of(dev)),
+                           "msg_feature_ball_hits")
+        return margin, count
+    dist = _host_dist2(q, r)
+    return (dist - radius2[None, :]).min(dim=1).values, (dist <= radius2[None, :]).sum(dim=1)
+
+
+def _poly_sums(x: torch.Tensor, y: torch.Tensor, ix: Optional[torch.Tensor], iy: Optional[torch.Tensor], gamma: float,
+               coef0: float, gpu: bool) -> torch.Tensor:
+    """float64 ``[S, 3]`` on the host: per subset the sums of ``k(u, v) = (gamma u.v + coef0)^3`` over the ordered pairs of
+    distinct positions of x's list, of y's list, and over all pairs of the two.  ``ix`` / ``iy``: int ``[S, m]`` row indices,
+    ``None``: every row once (one subset)."""
+    for idx, n in ((ix, x.shape[0]), (iy, y.shape[0])):
+        if idx is not None and (idx.ndim != 2 or idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise ValueError("an index list is empty or points outside its feature set")
+    S = 1 if ix is None and iy is None else (ix if ix is not None else iy).shape[0]
+    if (ix is not None and ix.shape[0] != S) or (iy is not None and iy.shape[0] != S):
+        raise ValueError("the two index lists differ in their number of subsets")
+    if gpu:
+        dev = _lib.require_gpu(x, y)
+        lib, d = _lib.lib(), x.shape[1]
+        ix = None if ix is None else ix.to(device=dev, dtype=torch.int32).contiguous()
+        iy = None if iy is None else iy.to(device=dev, dtype=torch.int32).contiguous()
+        mx = x.shape[0] if ix is None else ix.shape[1]
+        my = y.shape[0] if iy is None else iy.shape[1]
+        sums = torch.empty((S, 3), dtype=torch.float64, device=dev)
+        ws = _workspace(lib.msg_poly_mmd_workspace(x.shape[0], y.shape[0], d, S, mx, my), dev)
+        with _lib.on_device(dev):
+            with _lib.kernel_clock.span(("poly_mmd", S), 2.0 * S * d * (0.5 * mx * mx + 0.5 * my * my + mx * my)):
+                _lib.check(lib.msg_poly_mmd(x.data_ptr(), x.shape[0], y.data_ptr(), y.shape[0], d, _lib.ptr(ix), _lib.ptr(iy), S, mx,
+                                            my, float(gamma), float(coef0), sums.data_ptr(), ws.data_ptr(), _lib.stream_of(dev)),
+                           "msg_poly_mmd")
+        return sums.cpu()
+    out = torch.empty((S, 3), dtype=torch.float64)
+    for s in range(S):
+        xs = x if ix is None else x[ix[s].long()]
+        ys = y if iy is None else y[iy[s].long()]
+        kxx, kyy, kxy = ((gamma * (a @ b.t()) + coef0) ** 3 for a, b in ((xs, xs), (ys, ys), (xs, ys)))
+        out[s, 0], out[s, 1], out[s, 2] = kxx.sum() - kxx.diagonal().sum(), kyy.sum() - kyy.diagonal().sum(), kxy.sum()
+    return out
+
+
+def subset_indices(n: int, m: int, subsets: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """int32 ``[subsets, m]``: per subset ``m`` of ``n`` row indices drawn without replacement (the head of one
+    ``torch.randperm`` per subset, from ``generator`` or the global CPU generator)."""
+    if not 1 <= m <= n or subsets < 1:
+        raise ValueError(f"cannot draw {subsets} subsets of {m} rows out of {n}")
+    return torch.stack([torch.randperm(n, generator=generator)[:m] for _ in range(subsets)]).to(torch.int32)
+
+
+def _mmd2(sums: torch.Tensor, mx: int, my: int) -> float:
+    """The unbiased MMD^2 per subset from its three sums, float64 on the host, and the mean over the subsets."""
+    sums = sums.double()
+    per = sums[:, 0] / (mx * (mx - 1)) + sums[:, 1] / (my * (my - 1)) - 2.0 * sums[:, 2] / (mx * my)
+    return float(per.mean())
+
+
+def kernel_distance(real: torch.Tensor, fake: torch.Tensor, subsets: Optional[int] = None, subset_size: int = 1000,
+                    generator: Optional[torch.Generator] = None) -> float:
+    """Kernel inception distance of two feature sets ``[N, d]``, ``[M, d]``: the unbiased estimate of the squared maximum
+    mean discrepancy under the kernel ``k(u, v) = (u.v / d + 1)^3``.
+
+    ``subsets=None``: the full U-statistic over all rows, ``sum_{a != b} k(x_a, x_b) / (N (N - 1)) + sum_{a != b} k(y_a, y_b) /
+    (M (M - 1)) - 2 sum_{a, b} k(x_a, y_b) / (N M)`` -- the right form for a few hundred samples.  ``subsets=S``: the
+    StyleGAN2-ADA estimator, the mean of that statistic over ``S`` pairs of subsets of ``m = min(N, M, subset_size)`` rows drawn
+    without replacement (``subset_indices``, from ``generator``; the real set's lists are drawn first).
+
+    On the GPU the three sums of every subset come from one ``msg_poly_mmd`` call: fp32 products, every kernel value widened to
+    float64 before it is added, rows gathered by index while staging; the final combination is float64 on the host.  CPU tensors:
+    the same sums from float64 matrix products."""
+    gpu, (x, y) = _feature_sets(real, fake)
+    n, m_, d = x.shape[0], y.shape[0], x.shape[1]
+    if min(n, m_) < 2:
+        raise ValueError("the unbiased estimate needs at least two rows in each set")
+    if subsets is None:
+        return _mmd2(_poly_sums(x, y, None, None, 1.0 / d, 1.0, gpu), n, m_)
+    m = min(n, m_, int(subset_size))
+    if m < 2:
+        raise ValueError("subset_size is at least 2")
+    ix = subset_indices(n, m, int(subsets), generator)
+    iy = subset_indices(m_, m, int(subsets), generator)
+    return _mmd2(_poly_sums(x, y, ix, iy, 1.0 / d, 1.0, gpu), m, m)
+
+
+def manifold_scores(real: torch.Tensor, fake: torch.Tensor, k: int = 3) -> ManifoldScores:
+    """k-NN manifold precision and recall (Kynkaanniemi et al. 2019) and their outlier-robust forms density and coverage
+    (Naeem et al. 2020) of feature sets ``real [N, d]``, ``fake [M, d]``.  Every row carries a ball whose squared radius is its
+    squared distance to its k-th nearest neighbour within its OWN set (itself excluded by index: a duplicate row is a neighbour
+    at distance 0).
+
+    precision: the share of fake rows inside at least one real ball; recall: the share of real rows inside at least one fake
+    ball; density: the number of real balls a fake row lies in, summed over the fake rows, over ``k M``; coverage: the share of
+    real rows whose nearest fake row lies within the real row's own ball.  "Inside" is ``dist2 <= radius2``.
+
+    Distances do not change under a translation, but the fp32 error of ``|a|^2 + |b|^2 - 2 a.b`` grows with the norms: the mean of
+    the real rows is subtracted from BOTH sets first (one torch op each), then the kernels run -- ``msg_feature_knn`` for the radii
+    and the nearest fake row, ``msg_feature_ball_hits`` for margins and counts.  CPU tensors take the same definitions in float64
+    with distances as sums of squared differences."""
+    gpu, (x, y) = _feature_sets(real, fake)
+    k = int(k)
+    if not 1 <= k <= min(x.shape[0], y.shape[0]) - 1:
+        raise ValueError(f"k = {k} needs 1 <= k <= rows - 1 in both sets ({x.shape[0]}, {y.shape[0]} rows)")
+    if gpu and k > _lib.MSG_FEATURE_KNN_MAX:
+        raise ValueError(f"on the device k is at most {_lib.MSG_FEATURE_KNN_MAX}")
+    centre = x.mean(dim=0, keepdim=True)
+    x, y = x - centre, y - centre
+    radius_x, radius_y = _knn(x, x, k, True, gpu), _knn(y, y, k, True, gpu)
+    margin_y, count_y = _ball_hits(y, x, radius_x, gpu)
+    margin_x, _ = _ball_hits(x, y, radius_y, gpu)
+    nearest = _knn(x, y, 1, False, gpu)
+    stats = torch.stack([(margin_y <= 0).double().mean(), (margin_x <= 0).double().mean(),
+                         count_y.double().sum() / (k * y.shape[0]), (nearest <= radius_x).double().mean()]).tolist()
+    return ManifoldScores(*stats)
+
+
+class _Samples(_Metric):
+    """The sweep of ``_Frechet.__call__`` with the rows kept: the real rows are swept once and cached, every rank contributes
+    ``share = ceil(data_samples / ranks)`` rows of each kind and the rows are gathered in rank order, so every rank scores the
+    union.  ``input_size`` as for ``FID`` / ``FVD``."""
+
+    def __init__(self, *args, input_size: Optional[Tuple[int, int]] = None, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.input_size = input_size
+        self.rows_real = None
+
+    def _inputs(self, images: torch.Tensor, channel: int) -> torch.Tensor:
+        raise NotImplementedError
+
+    def _score(self, real: torch.Tensor, fake: torch.Tensor):
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def __call__(self, generator: nn.Module, dataset: Iterable):
+        net = self.network.to(self.device).eval()
+        channels = self._channels()
+        share = math.ceil(self.data_samples / _ranks())
+        if self.rows_real is None:
+            real = [FeatureRows(share) for _ in channels]
+            for real_images in dataset:
+                real_images = real_images.to(self.device)
+                for m, c in zip(real, channels):
+                    m.update(net(self._inputs(real_images, c)))
+                if real[0].full:
+                    break
+            real = [m.all_gather_() for m in real]
+            if real[0].n < self.data_samples:
+                warnings.warn(f"{type(self).__name__}: the dataset held {real[0].n} samples, fewer than data_samples = "
+                              f"{self.data_samples}; the real rows (cached from now on) are those {real[0].n}")
+            self.rows_real = [m.rows[:self.data_samples] for m in real]
+        generator.to(self.device).eval()
+        fake = [FeatureRows(share) for _ in channels]
+        for _ in range(math.ceil(share / self.batch_size)):
+            fake_images = generator(input=self._latents(generator))
+            for m, c in zip(fake, channels):
+                m.update(net(self._inputs(fake_images, c)))
+        fake = [m.all_gather_().rows[:self.data_samples] for m in fake]
+        return self._result([self._score(r, f) for r, f in zip(self.rows_real, fake)])
+
+
+class _KernelDistance(_Samples):
+    """``subsets`` / ``subset_size`` / ``generator`` as in ``kernel_distance``: the full U-statistic by default.  In a
+    multi-rank pass give every rank a ``generator`` with the same seed, or the ranks draw different subsets."""
+
+    def __init__(self, *args, subsets: Optional[int] = None, subset_size: int = 1000,
+                 generator: Optional[torch.Generator] = None, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.subsets, self.subset_size, self.generator = subsets, subset_size, generator
+
+    def _score(self, real, fake):
+        return kernel_distance(real, fake, self.subsets, self.subset_size, self.generator)
+
+
+class _Manifold(_Samples):
+    """``k``: the neighbour that sets a row's radius (3 in the precision / recall paper, 5 in density / coverage)."""
+
+    def __init__(self, *args, k: int = 3, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.k = k
+
+    def _score(self, real, fake):
+        return manifold_scores(real, fake, self.k)
+
+
+class KID(_KernelDistance):
+    """Kernel inception distance between dataset frames and generated frames: ``FID``'s inputs and network, scored by
+    ``kernel_distance``.  A float per channel."""
+    _inputs = FID._inputs
+
+
+class KVD(_KernelDistance):
+    """Kernel video distance: ``FVD``'s inputs and network, scored by ``kernel_distance``.  A float per channel."""
+    _inputs = FVD._inputs
+
+
+class PrecisionRecall(_Manifold):
+    """``manifold_scores`` of dataset frames against generated frames (``FID``'s inputs): a ``ManifoldScores`` per channel."""
+    _inputs = FID._inputs
+
+
+class PrecisionRecallVideo(_Manifold):
+    """``manifold_scores`` of dataset sequences against generated sequences (``FVD``'s inputs): a ``ManifoldScores`` per
+    channel."""
+    _inputs = FVD._inputs
