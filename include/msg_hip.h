@@ -924,6 +924,59 @@ long long msg_poly_mmd_workspace(int nx, int ny, int d, int S, int mx, int my);
 int msg_poly_mmd(const float* x, int nx, const float* y, int ny, int d, const int* ix, const int* iy, int S, int mx, int my,
                  float gamma, float coef0, double* sums, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Sliced Wasserstein kernels: what validation_metrics.py's SWD / SWVD (Karras et al. 2018, section 5: the sliced Wasserstein
+ * distance over 7 x 7 patches of a Laplacian pyramid) run on the device -- one pyramid level, the patch gather, the per-plane
+ * statistics, the projection with the normalisation folded in, the L1 distance of two sorted projections.  The sort between
+ * the last two is the caller's (torch.sort).  The [n, P 49] normalised copy and an [n, R] product are never written; the
+ * reference has no such metric.
+ * All tensors fp32, contiguous, 4-byte aligned (8 for the float64 sums and their ws); row offsets are 64-bit.  Where the
+ * shape allows, 16-byte aligned tensors are read / stored 16 bytes per lane, with the same bits as element by element (stated
+ * per entry).  No atomics; every output is bit-identical from run to run.  ws: the entry's _workspace(...) BYTES, needs no
+ * initialisation, carries nothing between calls.
+ * MSG_EINVAL (all five): a NULL pointer where none is allowed, a non-positive size, a misaligned pointer.  Nothing is launched
+ * and no output byte is written on refusal; the _workspace queries return -1 for sizes the entry refuses.
+ *
+ * msg_laplacian_level   fine [M, h, w] -> coarse [M, h/2, w/2] = down(fine) and lap [M, h, w] = fine - up(coarse); lap may be
+ *   NULL (the Gaussian pyramid only).  h and w even and >= 8, else MSG_EINVAL (also for more than 2^31 - 1 tiles of 32 x 64).
+ *   f = [1 4 6 4 1] / 16; boundary rule "mirror" on every axis: index -1 reads 1, -2 reads 2, n reads n - 2 (the edge sample is
+ *   not repeated; scipy.ndimage's mode="mirror").  Order of operations -- SEPARABLE, rows first, then columns:
+ *     down, per axis, on the five samples a b c d e around an even index:  fmaf(3/8, c, fmaf(1/4, b + d, (a + e) / 16))
+ *       -- the pairs are folded first, the scalings by 1/16 and 1/4 are exact: 3 roundings per axis, 6 for a coarse value;
+ *     up, per axis, on the zero-stuffed coarse samples with 2 f (4 F in two dimensions): an even index sees l c r of the coarse
+ *       axis as fmaf(3/4, c, (l + r) / 8) (2 roundings), an odd index between c and r sees (c + r) / 2 (1 rounding); with the
+ *       mirror rule on the stuffed axis coarse index -1 reads 1 and coarse index n/2 reads n/2 - 1;
+ *     lap = fine - up, one IEEE subtract: at most 6 + 2 + 2 + 1 = 11 roundings on the way to a lap value.
+ *   up() is taken of the ROUNDED coarse values, those the entry stores.  The source is read once per launch plus the tiles'
+ *   halo (4 rows above, 3 below, 4 columns left, 3 right); the halo's coarse values are recomputed per tile, with the same bits.
+ *   16-byte path: w % 4 == 0 and fine, lap 16-byte aligned (loads of fine, stores of lap; coarse is stored by element).
+ * msg_swd_gather   level [B, P, h, w]; pos int32 [B, K, 2] = (y, x) patch centres on the device; rows [B K, P 49]: row b K + k,
+ *   column 49 p + 7 dy + dx = level[b, p, y - 3 + dy, x - 3 + dx].  A plain copy: the bits of the source.  Positions are not
+ *   checked by the entry: a tap outside the plane reads as zero.  rows 16-byte aligned: stored 16 bytes per lane.
+ *   MSG_EINVAL also for B K > 2^31 - 1.
+ * msg_swd_plane_sums   rows [n, P 49] -> sums float64 [P, 2] = (sum x, sum x^2) over the n 49 values of each plane; every value
+ *   is widened to float64 before it is squared or added.  Fixed order: a workgroup sums 256 rows (a fixed lane assignment and a
+ *   fixed tree) into ws, a second launch merges the workgroups' partials in index order.  Read element by element (a plane's
+ *   runs of 49 floats have no common alignment).
+ * msg_swd_project   out [R, n] (direction-major: the sort runs along the contiguous axis),
+ *   out[r, i] = sum_j x^_ij dirs[j, r],  x^_ij = (rows[i, j] - mean[j / 49]) * istd[j / 49],  dirs [P 49, R], mean / istd [P].
+ *   x^ is formed in fp32 with an IEEE subtract and an IEEE multiply while the rows are staged; the sum is one fmaf chain in
+ *   ascending j from 0, on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32): P 49 roundings, P 49 + 2 with those of
+ *   x^.  Row tile 128, direction tile 128; one launch.  16-byte loads of rows when P 49 % 4 == 0 and rows is 16-byte aligned.
+ *   MSG_EINVAL also for more than 65535 direction tiles (what a block index addresses).
+ * msg_sorted_l1   a, b [R, n] -> sums float64 [R], sums[r] = sum_i |a[r, i] - b[r, i]|: difference and absolute value in fp32,
+ *   every term widened to float64 before it is added.  Fixed order: 4096 elements per workgroup into ws, merged in index order
+ *   by a second launch.  16-byte loads when n % 4 == 0 and a, b are 16-byte aligned.  MSG_EINVAL also for R > 65535.
+ * ------------------------------------------------------------------------- */
+int msg_laplacian_level(const float* fine, int M, int h, int w, float* coarse, float* lap, void* stream);
+int msg_swd_gather(const float* level, int B, int P, int h, int w, const int* pos, int K, float* rows, void* stream);
+long long msg_swd_plane_sums_workspace(int n, int P);
+int msg_swd_plane_sums(const float* rows, int n, int P, double* sums, void* ws, void* stream);
+int msg_swd_project(const float* rows, int n, int P, const float* mean, const float* istd, const float* dirs, int R,
+                    float* out, void* stream);
+long long msg_sorted_l1_workspace(int R, int n);
+int msg_sorted_l1(const float* a, const float* b, int R, int n, double* sums, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,8 @@ from .samples import (SheetWriter, dump_samples, epoch_sample_dump, interpolatio
 from .simulate import (TLFMDatasetWriter, bf_ranges_like, export_tlfm_batch, simulate_dataset, simulation_latents, write_tiff)
 from .tlfm_dataset import TFLMDatasetGAN, read_tiff
 from .validation_metrics import (FID, FVD, IS, KID, KVD, FeatureRows, ManifoldScores, PrecisionRecall, PrecisionRecallVideo,
-                                 kernel_distance, manifold_scores, metric_inputs)
+                                 kernel_distance, manifold_scores, metric_inputs, SWD, SWVD, laplacian_pyramid,
+                                 sliced_wasserstein)
 from .video import MjpegWriter, interpolation_video, jpeg_encode, jpeg_file, jpeg_tables
 
 __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper", "Draws", "PathLengthRegularization",
@@ -31,4 +32,4 @@ __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper
            "elastic_deform_batch", "ResidentTLFMStore", "ResidentTLFMFeed", "gather_tlfm_batch", "jpeg_tables", "jpeg_encode", "jpeg_file",
            "MjpegWriter", "interpolation_video", "export_tlfm_batch", "write_tiff", "TLFMDatasetWriter", "bf_ranges_like",
            "simulate_dataset", "simulation_latents", "KID", "KVD", "PrecisionRecall", "PrecisionRecallVideo", "FeatureRows",
-           "ManifoldScores", "kernel_distance", "manifold_scores"]
+           "ManifoldScores", "kernel_distance", "manifold_scores", "SWD", "SWVD", "laplacian_pyramid", "sliced_wasserstein"]

@@ -16,6 +16,7 @@ arrays and calls numpy / scipy.  Here a feature sweep folds each batch into runn
 of the SYMMETRIC matrix C_r^(1/2) C_f C_r^(1/2) (same spectrum as C_r C_f; ``eigh`` on the device, no complex arithmetic,
 eigenvalues clamped at zero where scipy's ``sqrtm(...).real`` drops an imaginary part).
 """
+import collections
 import functools
 import math
 import warnings
@@ -36,7 +37,8 @@ def _ranks() -> int:
 
 __all__ = ["IS", "FID", "FVD", "FeatureMoments", "frechet_distance", "frechet_distance_from_moments", "inception_score",
            "metric_inputs", "select_frames", "KID", "KVD", "PrecisionRecall", "PrecisionRecallVideo", "FeatureRows",
-           "ManifoldScores", "kernel_distance", "manifold_scores", "subset_indices"]
+           "ManifoldScores", "kernel_distance", "manifold_scores", "subset_indices", "SWD", "SWVD", "laplacian_pyramid",
+           "swd_positions", "swd_descriptors", "swd_directions", "sliced_wasserstein"]
 
 
 def select_frames(images: torch.Tensor, channel: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -678,3 +680,339 @@ class PrecisionRecallVideo(_Manifold):
     """``manifold_scores`` of dataset sequences against generated sequences (``FVD``'s inputs): a ``ManifoldScores`` per
     channel."""
     _inputs = FVD._inputs
+
+
+# ------------------------------------------------------------------------------------------- sliced Wasserstein distance
+# SWD / SWVD (DESIGN.md section 5, "Sliced Wasserstein distance"; Karras et al. 2018, section 5): the one metric here that
+# needs no feature network.  Per level of a Laplacian pyramid, 7 x 7 patches of both sets are normalised per plane, projected
+# on random unit directions, sorted, and compared by the mean absolute difference.  On the GPU the level, the gather, the
+# statistics, the projection (normalisation folded in) and the final reduction are csrc/swd.hip; the sort is torch.sort.
+# CPU tensors take the float64 statement of the same definition.
+_SWD_PATCH = 7
+_SWD_TAPS = _SWD_PATCH * _SWD_PATCH
+
+
+def _pyramid_sizes(h: int, w: int, min_size: int):
+    if min_size < 1:
+        raise ValueError(f"min_size is at least 1, not {min_size}")
+    levels = 1
+    while min(h, w) >> levels >= min_size:
+        levels += 1
+    if h % (1 << (levels - 1)) or w % (1 << (levels - 1)):
+        raise ValueError(f"{h} x {w} frames are not divisible by 2^{levels - 1} (a pyramid of {levels} levels down to a "
+                         f"shorter side >= {min_size})")
+    return [(h >> l, w >> l) for l in range(levels)]
+
+
+def _host_filter(x: torch.Tensor, gain: float) -> torch.Tensor:
+    """``x [N, 1, h, w]`` float64 convolved with ``gain * f f^T``, ``f = [1, 4, 6, 4, 1] / 16``, boundary rule "mirror" (torch's
+    ``reflect`` padding: the edge sample is not repeated)."""
+    f = torch.tensor([1.0, 4.0, 6.0, 4.0, 1.0], dtype=torch.float64) / 16.0
+    kernel = (gain * torch.outer(f, f))[None, None]
+    return torch.nn.functional.conv2d(torch.nn.functional.pad(x, (2, 2, 2, 2), mode="reflect"), kernel)
+
+
+def laplacian_pyramid(frames: torch.Tensor, min_size: int = 16) -> list:
+    """The Laplacian pyramid of ``frames [..., H, W]``, finest level first: ``G_0`` the frames, ``G_(l+1) = down(G_l)`` (the
+    binomial ``F = f f^T``, ``f = [1, 4, 6, 4, 1] / 16``, boundary rule "mirror", then every second row and column), level ``l`` is
+    ``G_l - up(G_(l+1))`` (``up``: the samples on the even positions of a zero array of twice the size, convolved with ``4 F``), the
+    coarsest level is ``G_L`` itself.  Levels run down to the last one whose shorter side is >= ``min_size``; ``H`` and ``W`` must
+    be divisible by ``2^(levels - 1)``.
+
+    fp32 tensors on the GPU: one ``msg_laplacian_level`` launch per level, fp32 out (sides below 8 are refused there).  CPU
+    tensors: the float64 statement, float64 out."""
+    if frames.ndim < 2:
+        raise ValueError(f"expected [..., H, W] frames, got {tuple(frames.shape)}")
+    lead, (h, w) = frames.shape[:-2], frames.shape[-2:]
+    sizes = _pyramid_sizes(h, w, int(min_size))
+    frames = frames.detach()
+    if frames.is_cuda:
+        dev = _lib.require_gpu(frames)
+        g = frames.to(torch.float32).contiguous().view(-1, h, w)
+        lib, levels = _lib.lib(), []
+        with _lib.on_device(dev):
+            for (fh, fw), (ch, cw) in zip(sizes[:-1], sizes[1:]):
+                coarse = torch.empty((g.shape[0], ch, cw), dtype=torch.float32, device=dev)
+                lap = torch.empty_like(g)
+                with _lib.kernel_clock.span(("laplacian_level", fh, fw), 4.0 * (2.25 * g.numel())):
+                    _lib.check(lib.msg_laplacian_level(g.data_ptr(), g.shape[0], fh, fw, coarse.data_ptr(), lap.data_ptr(),
+                                                       _lib.stream_of(dev)), "msg_laplacian_level")
+                levels.append(lap.view(*lead, fh, fw))
+                g = coarse
+        levels.append(g.view(*lead, *sizes[-1]) if len(sizes) > 1 else g.view(*lead, h, w).clone())
+        return levels
+    g = frames.to(torch.float64).reshape(-1, 1, h, w)
+    levels = []
+    for fh, fw in sizes[:-1]:
+        coarse = _host_filter(g, 1.0)[..., ::2, ::2]
+        stuffed = torch.zeros_like(g)
+        stuffed[..., ::2, ::2] = coarse
+        levels.append((g - _host_filter(stuffed, 4.0)).reshape(*lead, fh, fw))
+        g = coarse
+    levels.append(g.reshape(*lead, *sizes[-1]).clone())
+    return levels
+
+
+def swd_positions(samples: int, h: int, w: int, descriptors_per_image: int = 128,
+                  generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """int32 ``[samples, descriptors_per_image, 2]`` on the host: patch centres ``(y, x)`` drawn uniformly from ``[3, h - 4] x
+    [3, w - 4]`` (all ``y`` of the call first, then all ``x``; from ``generator`` or the global CPU generator), so that every 7 x 7
+    patch lies inside its plane."""
+    if samples < 1 or descriptors_per_image < 1 or min(h, w) < _SWD_PATCH:
+        raise ValueError(f"cannot draw {descriptors_per_image} patches of 7 x 7 per sample from {samples} planes of {h} x {w}")
+    y = torch.randint(3, h - 3, (samples, descriptors_per_image), generator=generator)
+    x = torch.randint(3, w - 3, (samples, descriptors_per_image), generator=generator)
+    return torch.stack([y, x], dim=2).to(torch.int32)
+
+
+def swd_descriptors(level: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """The patches of ``level [B, P, h, w]`` centred at ``pos [B, K, 2]`` as rows ``[B K, P 49]``: plane-major, then patch row,
+    then patch column.  A tap outside the plane reads as zero.  fp32 on the GPU (``msg_swd_gather``, a copy), the level's own
+    dtype on the host."""
+    if level.ndim != 4 or pos.ndim != 3 or pos.shape[0] != level.shape[0] or pos.shape[2] != 2:
+        raise ValueError(f"expected a [B, P, h, w] level and [B, K, 2] positions, got {tuple(level.shape)}, {tuple(pos.shape)}")
+    B, P, h, w = level.shape
+    K = pos.shape[1]
+    level = level.detach()
+    if level.is_cuda:
+        dev = _lib.require_gpu(level)
+        level = level.to(torch.float32).contiguous()
+        pos = pos.to(device=dev, dtype=torch.int32).contiguous()
+        rows = torch.empty((B * K, P * _SWD_TAPS), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            with _lib.kernel_clock.span(("swd_gather", P), 8.0 * rows.numel()):
+                _lib.check(_lib.lib().msg_swd_gather(level.data_ptr(), B, P, h, w, pos.data_ptr(), K, rows.data_ptr(),
+                                                     _lib.stream_of(dev)), "msg_swd_gather")
+        return rows
+    pos = pos.long()
+    off = torch.arange(-3, 4)
+    y = pos[:, :, 0, None, None] + off[None, None, :, None]                    # [B, K, 7, 1]
+    x = pos[:, :, 1, None, None] + off[None, None, None, :]                    # [B, K, 1, 7]
+    inside = ((y >= 0) & (y < h) & (x >= 0) & (x < w))[:, :, None]             # [B, K, 1, 7, 7]
+    b = torch.arange(B)[:, None, None, None, None]
+    p = torch.arange(P)[None, None, :, None, None]
+    taps = level[b, p, y.clamp(0, h - 1)[:, :, None], x.clamp(0, w - 1)[:, :, None]]
+    return (taps * inside.to(taps.dtype)).reshape(B * K, P * _SWD_TAPS)
+
+
+def swd_directions(d: int, repeats: int = 4, directions: int = 128, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """fp32 ``[repeats, d, directions]`` on the host: per repeat one ``torch.randn([d, directions])`` draw (from ``generator`` or
+    the global CPU generator), every column scaled to unit length in float64 and rounded once to fp32."""
+    if d < 1 or repeats < 1 or directions < 1:
+        raise ValueError(f"cannot draw {repeats} x {directions} directions of width {d}")
+    out = []
+    for _ in range(repeats):
+        draw = torch.randn([d, directions], generator=generator).double()
+        out.append((draw / draw.square().sum(dim=0, keepdim=True).sqrt()).float())
+    return torch.stack(out)
+
+
+def _plane_statistics(rows: torch.Tensor, planes: int, gpu: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 ``mean [P]`` and ``istd [P]`` = 1 / population standard deviation over all ``n 49`` values of each plane, on the
+    host; both from float64 and rounded once.  A constant plane has ``istd = inf``."""
+    n = rows.shape[0]
+    count = float(n * _SWD_TAPS)
+    if gpu:
+        dev = _lib.require_gpu(rows)
+        lib = _lib.lib()
+        sums = torch.empty((planes, 2), dtype=torch.float64, device=dev)
+        ws = _workspace(lib.msg_swd_plane_sums_workspace(n, planes), dev)
+        with _lib.on_device(dev):
+            with _lib.kernel_clock.span(("swd_plane_sums", planes), 4.0 * rows.numel()):
+                _lib.check(lib.msg_swd_plane_sums(rows.data_ptr(), n, planes, sums.data_ptr(), ws.data_ptr(), _lib.stream_of(dev)),
+                           "msg_swd_plane_sums")
+        sums = sums.cpu()
+        mean, square = sums[:, 0] / count, sums[:, 1] / count
+        var = square - mean * mean
+        # sum x^2 / N - mean^2 cancels when the spread is far below the mean; below 2^-36 of the mean square it is in the
+        # rounding noise of the float64 sums, and the plane is measured directly
+        doubtful = (var <= square * 2.0 ** -36).nonzero().flatten().tolist()
+    else:
+        x = rows.reshape(n, planes, _SWD_TAPS).transpose(0, 1).reshape(planes, -1)
+        mean = x.mean(dim=1)
+        var = (x - mean[:, None]).square().mean(dim=1)
+        doubtful = list(range(planes))
+    for p in doubtful:
+        x = rows.reshape(n, planes, _SWD_TAPS)[:, p]
+        lo, hi = float(x.min()), float(x.max())
+        if lo == hi:                                    # a constant plane, decided exactly: std = 0
+            mean[p], var[p] = lo, 0.0
+        elif gpu:
+            x = x.double()
+            mean[p] = float(x.sum()) / count
+            var[p] = float((x - mean[p]).square().sum()) / count
+    return mean.float(), (1.0 / var.sqrt()).float()
+
+
+def _project_sorted(rows: torch.Tensor, planes: int, mean: torch.Tensor, istd: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
+    """Device: ``[R, n]`` fp32, the normalised rows projected on ``dirs [d, R]`` (``msg_swd_project``), every direction sorted
+    ascending."""
+    dev, lib = rows.device, _lib.lib()
+    n, R = rows.shape[0], dirs.shape[1]
+    out = torch.empty((R, n), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        with _lib.kernel_clock.span(("swd_project", planes, R), 2.0 * n * R * rows.shape[1]):
+            _lib.check(lib.msg_swd_project(rows.data_ptr(), n, planes, mean.data_ptr(), istd.data_ptr(), dirs.data_ptr(), R,
+                                           out.data_ptr(), _lib.stream_of(dev)), "msg_swd_project")
+    return torch.sort(out, dim=1).values
+
+
+def sliced_wasserstein(real_rows: torch.Tensor, fake_rows: torch.Tensor, planes: int, repeats: int = 4, directions: int = 128,
+                       generator: Optional[torch.Generator] = None, normalize: bool = True) -> float:
+    """The sliced Wasserstein distance of two descriptor sets ``[n, planes * 49]`` of EQUAL ``n``, times 1000.
+
+    Each set is normalised per plane (its mean and population standard deviation over all ``n 49`` values of the plane, from
+    float64 sums, rounded once to fp32 ``mean`` and ``istd = 1 / std``; ``normalize=False``: mean 0, istd 1).  ``repeats`` x
+    ``directions`` unit directions come from ``swd_directions(planes * 49, repeats, directions, generator)``; for every direction
+    both sets' normalised rows are projected, each projection is sorted ascending, and the result is ``1000 mean |a_(i) -
+    b_(i)|`` over rows and directions.  A constant plane in either set gives NaN.
+
+    On the GPU, one repeat at a time: ``msg_swd_plane_sums`` -> ``msg_swd_project`` (the normalisation happens while the rows
+    are staged; no normalised copy and no ``[n, R]`` product are written) -> ``torch.sort(dim=1)`` on the direction-major
+    ``[directions, n]`` array -> ``msg_sorted_l1`` (float64 sums); two sorted ``[directions, n]`` arrays are live at its end.  CPU
+    tensors take the float64 statement with the same fp32-rounded ``mean``, ``istd`` and directions."""
+    gpu, (x, y) = _feature_sets(real_rows, fake_rows)
+    planes = int(planes)
+    if planes < 1 or x.shape[1] != planes * _SWD_TAPS:
+        raise ValueError(f"rows of width {x.shape[1]} are not {planes} planes of 7 x 7")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError(f"the two sets hold {x.shape[0]} and {y.shape[0]} rows: the sorted projections are compared row by row")
+    n, d = x.shape
+    stats = []
+    for s in (x, y):
+        if normalize:
+            stats.append(_plane_statistics(s, planes, gpu))
+        else:
+            stats.append((torch.zeros(planes), torch.ones(planes)))
+    dirs = swd_directions(d, int(repeats), int(directions), generator)
+    if not all(bool(torch.isfinite(istd).all()) for _, istd in stats):
+        return math.nan
+    if gpu:
+        dev = _lib.require_gpu(x, y)
+        lib = _lib.lib()
+        stats = [(m.to(dev), i.to(dev)) for m, i in stats]
+        R = dirs.shape[2]
+        sums = torch.empty(R, dtype=torch.float64, device=dev)
+        ws = _workspace(lib.msg_sorted_l1_workspace(R, n), dev)
+        total = torch.zeros((), dtype=torch.float64, device=dev)
+        for rep in range(dirs.shape[0]):
+            dr = dirs[rep].to(dev).contiguous()
+            a = _project_sorted(x, planes, stats[0][0], stats[0][1], dr)
+            b = _project_sorted(y, planes, stats[1][0], stats[1][1], dr)
+            with _lib.on_device(dev):
+                with _lib.kernel_clock.span(("sorted_l1", R), 8.0 * R * n):
+                    _lib.check(lib.msg_sorted_l1(a.data_ptr(), b.data_ptr(), R, n, sums.data_ptr(), ws.data_ptr(),
+                                                 _lib.stream_of(dev)), "msg_sorted_l1")
+            total += sums.sum()
+            del a, b
+        return 1000.0 * float(total) / (float(n) * dirs.shape[0] * dirs.shape[2])
+    total = 0.0
+    for rep in range(dirs.shape[0]):
+        proj = []
+        for s, (mean, istd) in zip((x, y), stats):
+            hat = (s.reshape(n, planes, _SWD_TAPS) - mean.double()[None, :, None]) * istd.double()[None, :, None]
+            proj.append((hat.reshape(n, d) @ dirs[rep].double()).sort(dim=0).values)
+        total += float((proj[0] - proj[1]).abs().sum())
+    return 1000.0 * total / (float(n) * dirs.shape[0] * dirs.shape[2])
+
+
+@functools.lru_cache(maxsize=None)
+def _swd_score_type(sides: Tuple[int, ...]):
+    return collections.namedtuple("SlicedWassersteinScores", ("mean",) + tuple(f"r{s}" for s in sides))
+
+
+class _SlicedWasserstein(_Metric):
+    """The sweep of ``_Samples.__call__`` on pixels: no feature network.  Per channel and pyramid level the real descriptor rows
+    are kept in ``FeatureRows`` and cached across calls; every rank contributes ``share = ceil(data_samples / ranks)`` samples of
+    each kind and the rows are gathered in rank order; the generator sweep draws exactly as many sequences as the real sweep
+    kept.  Patch positions and directions come from ``generator`` (``None``: the global CPU generator).  In a multi-rank pass
+    give every rank a ``generator`` with the same seed, or the ranks draw different directions.
+
+    The score per channel is a named tuple ``(mean, r<side>, ...)``: one field per level named by the level's height, finest
+    first (256 x 256 frames: ``mean, r256, r128, r64, r32, r16``), ``mean`` their average.  A level one of whose planes is
+    constant over a whole set scores NaN, with one warning per channel and level."""
+
+    def __init__(self, device: Union[str, torch.device] = "cuda", data_parallel: bool = False, batch_size: int = 1,
+                 data_samples: int = 5000, no_rfp: bool = False, no_gfp: bool = False, descriptors_per_image: int = 128,
+                 repeats: int = 4, directions: int = 128, min_size: int = 16,
+                 generator: Optional[torch.Generator] = None) -> None:
+        self.network = None
+        self.device, self.batch_size, self.data_samples = device, batch_size, data_samples
+        self.no_rfp, self.no_gfp = no_rfp, no_gfp
+        self.descriptors_per_image, self.repeats, self.directions = int(descriptors_per_image), int(repeats), int(directions)
+        self.min_size, self.generator = int(min_size), generator
+        self.rows_real = None                           # [channel][level] -> [n, P 49], cached across calls
+        self._warned: set = set()
+
+    def _inputs(self, images: torch.Tensor, channel: int) -> torch.Tensor:
+        raise NotImplementedError
+
+    def _fold(self, images: torch.Tensor, channel: int, into: Optional[list], limit: int) -> list:
+        """One batch's descriptor rows of every level, appended to ``into`` (a ``FeatureRows`` per level)."""
+        planes = self._inputs(images, channel)[:, 0]                           # [B, T', H, W]: the frames are the planes
+        levels = laplacian_pyramid(planes, self.min_size)
+        self._sides = [level.shape[2] for level in levels]
+        if into is None:
+            into = [FeatureRows(limit * self.descriptors_per_image) for _ in levels]
+        for level, rows in zip(levels, into):
+            pos = swd_positions(level.shape[0], level.shape[2], level.shape[3], self.descriptors_per_image, self.generator)
+            rows.update(swd_descriptors(level, pos))
+        return into
+
+    @torch.no_grad()
+    def __call__(self, generator: nn.Module, dataset: Iterable):
+        channels, K = self._channels(), self.descriptors_per_image
+        share = math.ceil(self.data_samples / _ranks())
+        if self.rows_real is None:
+            real = [None for _ in channels]
+            for real_images in dataset:
+                real_images = real_images.to(self.device)
+                for k, c in enumerate(channels):
+                    real[k] = self._fold(real_images, c, real[k], share)
+                if real[0][0].full:
+                    break
+            if real[0] is None:
+                raise ValueError("the dataset is empty")
+            real = [[m.all_gather_() for m in levels] for levels in real]
+            if real[0][0].n < self.data_samples * K:
+                warnings.warn(f"{type(self).__name__}: the dataset held {real[0][0].n // K} samples, fewer than data_samples = "
+                              f"{self.data_samples}; the real rows (cached from now on) are those {real[0][0].n // K}")
+            self.rows_real = [[m.rows[:self.data_samples * K] for m in levels] for levels in real]
+        kept = self.rows_real[0][0].shape[0] // K
+        share = math.ceil(kept / _ranks())
+        generator.to(self.device).eval()
+        fake = [None for _ in channels]
+        for _ in range(math.ceil(share / self.batch_size)):
+            fake_images = generator(input=self._latents(generator))
+            for k, c in enumerate(channels):
+                fake[k] = self._fold(fake_images, c, fake[k], share)
+        scores = []
+        for c, real_levels, fake_levels in zip(channels, self.rows_real, fake):
+            per_level = []
+            for side, real_rows, rows in zip(self._sides, real_levels, fake_levels):
+                fake_rows = rows.all_gather_().rows[:kept * K]
+                value = sliced_wasserstein(real_rows, fake_rows, real_rows.shape[1] // _SWD_TAPS, self.repeats, self.directions,
+                                           self.generator)
+                if math.isnan(value) and (c, side) not in self._warned:
+                    self._warned.add((c, side))
+                    warnings.warn(f"{type(self).__name__}: channel {c}, level r{side}: a plane is constant over a whole set, "
+                                  "its standard deviation is 0 and the level's score is NaN")
+                per_level.append(value)
+            scores.append(_swd_score_type(tuple(self._sides))(sum(per_level) / len(per_level), *per_level))
+        return self._result(scores)
+
+
+class SWD(_SlicedWasserstein):
+    """Sliced Wasserstein distance between dataset frames and generated frames: channel ``c`` of one drawn time step (as ``FID``
+    draws it) at its own size and intensity scale, ``metric_inputs(..., size=None, normalize=None, planes=1)``."""
+
+    def _inputs(self, images, channel):
+        return metric_inputs(images, channel, t=_draw_time_step(images), size=None, normalize=None, planes=1)
+
+
+class SWVD(_SlicedWasserstein):
+    """Sliced Wasserstein video distance: the whole clip of channel ``c`` (as ``FVD`` takes it); the ``T`` frames are the
+    planes of a patch, so a descriptor spans time."""
+
+    def _inputs(self, images, channel):
+        return metric_inputs(images, channel, t=None, size=None, normalize=None, planes=1)
