@@ -977,6 +977,55 @@ int msg_swd_project(const float* rows, int n, int P, const float* mean, const fl
 long long msg_sorted_l1_workspace(int R, int n);
 int msg_sorted_l1(const float* a, const float* b, int R, int n, double* sums, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Structural similarity, one scale: what ssim.py's ms_ssim (Wang et al. 2003; the diversity metric MSSSIM / MSSSIMVideo of
+ * validation_metrics.py, the image loss of project.py) runs on the device -- per plane pair the sums of the contrast-structure
+ * map cs and of the SSIM map cs l over the valid window positions, optionally the sum of |x - y| over all pixels and both
+ * planes halved by the 2 x 2 mean for the next scale, in one launch (plus the merge of the tiles' partial sums); and the
+ * gradient of those three MEANS with respect to x in one more.  The five moment maps are never written to memory; x and y are
+ * read once per launch plus the tiles' halo.  The combination of the scales (a few values per plane) is the caller's.  The
+ * reference has no such function.
+ * Window: 11 taps g_k = exp(-(k - 5)^2 / (2 1.5^2)) / sum, computed in float64 and rounded once to fp32; separable, "valid": a
+ * plane h x w has (h - 10)(w - 10) positions, position (i, j) covers pixels (i .. i + 10, j .. j + 10).
+ * All tensors fp32, contiguous, 4-byte aligned (8 for the float64 sums and ws); plane offsets are 64-bit.  16-byte path (both
+ * entries): w % 4 == 0 and x, y (and grad_x) 16-byte aligned -> the patches are loaded and grad_x is stored 16 bytes per lane;
+ * only the memory instructions differ, the bits are those of the element-by-element path.  No atomics; every output is
+ * bit-identical from run to run.  ws: msg_ssim_scale_workspace(M, h, w) BYTES (24 per tile), needs no initialisation, carries
+ * nothing between calls; -1 for a size the entry refuses.
+ * MSG_EINVAL (both): a NULL pointer where none is allowed, h or w < 11, M <= 0, a misaligned pointer, only one of x_half /
+ * y_half, more than 2^31 - 1 tiles (16 x 64 forward, 16 x 32 backward).  Nothing is launched and no output byte is written.
+ *
+ * msg_ssim_scale   x, y [M, h, w]; c1 = (0.01 R)^2, c2 = (0.03 R)^2 for a data range R; sums float64 [M, 2] = (sum cs, sum cs l)
+ *   over the positions; l1 float64 [M] = sum |x - y| over the h w pixels, or NULL; x_half, y_half [M, h / 2, w / 2] (floor; an
+ *   odd trailing row or column is dropped), both or neither.  Order of operations, all fp32, every operation rounded once:
+ *     xx = x x, yy = y y, xy = x y are ROUNDED to fp32 per pixel before any filtering;
+ *     SEPARABLE, rows first, then columns.  Each pass of each of the five maps (x, y, xx, yy, xy) is one chain in ascending tap
+ *       k: g_0 v_0 (a multiply), then fmaf(g_k, v_k, acc) for k = 1 .. 10 -- 11 roundings per pass, 22 + 1 for a second moment;
+ *     mu_x mu_x, mu_y mu_y, mu_x mu_y rounded; s_xx = E_xx - mu_x mu_x, s_yy, s_xy likewise (one subtract each);
+ *     D2 = (s_xx + s_yy) + c2, D1 = (mu_x mu_x + mu_y mu_y) + c1; cs = fmaf(2, s_xy, c2) / D2, l = fmaf(2, mu_x mu_y, c1) / D1
+ *       (IEEE divisions); the SSIM term is the rounded product cs l;
+ *     |x - y|: one subtract;  half = 0.25 ((v00 + v01) + (v10 + v11)): three roundings.
+ *   Every cs, cs l and |x - y| term is widened to float64 before it is added.  Fixed order: a lane adds its four positions (its
+ *   four pixels) in row order, a wave folds its lanes by shuffles (a fixed tree), the four wave sums are added in wave order into
+ *   ws, and a second launch adds a plane's tiles in index order (row-major).
+ * msg_ssim_scale_backward   g [M, 3] fp32: the gradients with respect to the plane's MEAN cs, MEAN cs l and MEAN |x - y|; the
+ *   entry divides them by the counts (h - 10)(w - 10), (h - 10)(w - 10) and h w, each converted to fp32 (IEEE divisions): gcs,
+ *   gss, gl1.  g_half [M, h / 2, w / 2] or NULL: the gradient with respect to x_half.  grad_x [M, h, w]: every element written.
+ *   One launch; the moments are recomputed per 16 x 32 tile of grad_x from its 10-pixel halo with the forward's operations.  Per
+ *   position:  a = fmaf(gss, l, gcs), b = gss cs, t2 = a / D2, t1 = b / D1,
+ *     A = fmaf(t2, 2 (mu_x cs - mu_y), t1 (2 (mu_y - mu_x l))),  B = -(t2 cs),  C = 2 t2   (zero where there is no position);
+ *   per pixel p the transposed window GA = sum_k sum_k' g_k g_k' A[p - (k, k')] (likewise GB, GC): rows first (tap k takes the
+ *   position k columns to the left), then columns, each an ascending-tap chain as above;
+ *     grad = fmaf(y, GC, fmaf(2 x, GB, GA));  grad = fmaf(gl1, sign(x - y), grad) with sign(0) = 0;
+ *     with g_half, for pixels inside the 2 (h / 2) x 2 (w / 2) block:  grad = fmaf(0.25, g_half[p / 2], grad).
+ *   SSIM is symmetric: the gradient with respect to y is the same call with x and y exchanged.
+ * ------------------------------------------------------------------------- */
+long long msg_ssim_scale_workspace(int M, int h, int w);
+int msg_ssim_scale(const float* x, const float* y, int M, int h, int w, float c1, float c2, double* sums, double* l1,
+                   float* x_half, float* y_half, void* ws, void* stream);
+int msg_ssim_scale_backward(const float* x, const float* y, const float* g, const float* g_half, int M, int h, int w,
+                            float c1, float c2, float* grad_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

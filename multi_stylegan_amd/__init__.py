@@ -19,7 +19,9 @@ from .simulate import (TLFMDatasetWriter, bf_ranges_like, export_tlfm_batch, sim
 from .tlfm_dataset import TFLMDatasetGAN, read_tiff
 from .validation_metrics import (FID, FVD, IS, KID, KVD, FeatureRows, ManifoldScores, PrecisionRecall, PrecisionRecallVideo,
                                  kernel_distance, manifold_scores, metric_inputs, SWD, SWVD, laplacian_pyramid,
-                                 sliced_wasserstein)
+                                 sliced_wasserstein, MSSSIM, MSSSIMVideo, DiversityScore)
+from .ssim import MS_SSIM_WEIGHTS, ms_ssim, ssim_levels
+from .project import Projection, mean_latent, project_sequences, truncate
 from .video import MjpegWriter, interpolation_video, jpeg_encode, jpeg_file, jpeg_tables
 
 __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper", "Draws", "PathLengthRegularization",
@@ -32,4 +34,6 @@ __all__ = ["MultiStyleGANGenerator", "MultiStyleGANDiscriminator", "ModelWrapper
            "elastic_deform_batch", "ResidentTLFMStore", "ResidentTLFMFeed", "gather_tlfm_batch", "jpeg_tables", "jpeg_encode", "jpeg_file",
            "MjpegWriter", "interpolation_video", "export_tlfm_batch", "write_tiff", "TLFMDatasetWriter", "bf_ranges_like",
            "simulate_dataset", "simulation_latents", "KID", "KVD", "PrecisionRecall", "PrecisionRecallVideo", "FeatureRows",
-           "ManifoldScores", "kernel_distance", "manifold_scores", "SWD", "SWVD", "laplacian_pyramid", "sliced_wasserstein"]
+           "ManifoldScores", "kernel_distance", "manifold_scores", "SWD", "SWVD", "laplacian_pyramid", "sliced_wasserstein",
+           "MSSSIM", "MSSSIMVideo", "DiversityScore", "ms_ssim", "ssim_levels", "MS_SSIM_WEIGHTS", "Projection", "mean_latent",
+           "project_sequences", "truncate"]

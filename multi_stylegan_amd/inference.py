@@ -35,10 +35,13 @@ class GeneratorSampler:
     crossover is drawn once here because a captured graph has a fixed structure).
     ``randomize_noise=False`` uses the generator's registered noise buffers (model_wrapper.py:156), ``True`` draws fresh
     per-layer noise inside the graph (graph-safe Philox offsets: every replay gets new noise).
+    ``latent_shape``: the inputs are W ``(D,)`` or W+ ``(n, D)`` latents of that shape per sample and go to the generator with
+    ``input_is_latent=True`` (not with ``mixing``); ``None``: ``z`` as above.
     """
 
     def __init__(self, generator: nn.Module, batch_size: int = 1, randomize_noise: bool = True, mixing: bool = False,
-                 inject_index: Optional[int] = None, use_graph: bool = True, device: Union[str, torch.device] = "cuda"):
+                 inject_index: Optional[int] = None, use_graph: bool = True, device: Union[str, torch.device] = "cuda",
+                 latent_shape: Optional[Tuple[int, ...]] = None):
         self.generator = generator.to(device).eval().requires_grad_(False)
         self.device = torch.device(device)
         self.batch_size, self.randomize_noise, self.mixing = batch_size, randomize_noise, mixing
@@ -47,7 +50,10 @@ class GeneratorSampler:
             inject_index = n_latents // 2
         self.inject_index = inject_index
         ld = generator.latent_dimensions
-        self._z = [torch.zeros(batch_size, ld, device=self.device) for _ in range(2 if mixing else 1)]
+        if latent_shape is not None and mixing:
+            raise ValueError("W / W+ latents are not mixed: latent_shape needs mixing=False")
+        self.latent_shape = None if latent_shape is None else tuple(int(s) for s in latent_shape)
+        self._z = [torch.zeros(batch_size, *(self.latent_shape or (ld,)), device=self.device) for _ in range(2 if mixing else 1)]
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._image: Optional[torch.Tensor] = None
         self._stamps: Optional[tuple] = None
@@ -55,6 +61,8 @@ class GeneratorSampler:
 
     def _forward(self) -> torch.Tensor:
         z = self._z if self.mixing else self._z[0]
+        if self.latent_shape is not None:
+            return self.generator(z, randomize_noise=self.randomize_noise, input_is_latent=True)
         return self.generator(z, randomize_noise=self.randomize_noise, inject_index=self.inject_index)
 
     def _weight_stamps(self) -> tuple:

@@ -369,22 +369,33 @@ def interpolation_latents(anchors: torch.Tensor, steps_per_anchor: int = 100) ->
 @torch.no_grad()
 def interpolation_frames(generator_or_checkpoint, directory: str, anchors: Union[int, torch.Tensor] = 16,
                          steps_per_anchor: int = 100, batch_size: int = 32, seed: Optional[int] = None, use_graph: bool = True,
-                         writer: Optional[SheetWriter] = None) -> int:
+                         writer: Optional[SheetWriter] = None, anchors_are_latents: bool = False) -> int:
     """scripts/gan_latent_space_interpolation.py:28-59 without its ffmpeg call: ``frame_{index:05d}.png`` in ``directory`` for
     every interpolated latent, each the channels' sheets stacked top to bottom (bright field over GFP).  Returns their number.
 
     ``anchors``: a ``[K, D]`` tensor, or K for ``torch.randn(K, D, generator=torch.Generator().manual_seed(seed))`` drawn on the
     host (``seed=None``: the global generator).  Batches are ``batch_size`` consecutive latents, ``randomize_noise=False``; a
-    trailing partial batch is padded with its last latent and the padding is not written."""
+    trailing partial batch is padded with its last latent and the padding is not written.
+    ``anchors_are_latents=True``: ``anchors`` is a ``[K, D]`` (W) or ``[K, n, D]`` (W+, e.g. ``project.project_sequences(...).latent``)
+    tensor, interpolated the same way and handed to the generator with ``input_is_latent=True``."""
     from .inference import GeneratorSampler
     device = _device_of(generator_or_checkpoint)
     generator = _generator_of(generator_or_checkpoint, device)
+    latent_shape = None
+    if anchors_are_latents:
+        if not isinstance(anchors, torch.Tensor) or anchors.ndim not in (2, 3):
+            raise ValueError("anchors_are_latents=True takes [K, D] or [K, n, D] W / W+ anchors")
+        latent_shape = tuple(anchors.shape[1:])
+        anchors = anchors.reshape(anchors.shape[0], -1)
     if not isinstance(anchors, torch.Tensor):
         draw = None if seed is None else torch.Generator().manual_seed(int(seed))
         anchors = torch.randn(int(anchors), generator.latent_dimensions, generator=draw)
     latents = interpolation_latents(anchors.to(device=device, dtype=torch.float32), steps_per_anchor)
     total = latents.shape[0]
-    sampler = GeneratorSampler(generator, batch_size=batch_size, randomize_noise=False, use_graph=use_graph, device=device)
+    if latent_shape is not None:
+        latents = latents.reshape(total, *latent_shape)
+    sampler = GeneratorSampler(generator, batch_size=batch_size, randomize_noise=False, use_graph=use_graph, device=device,
+                               latent_shape=latent_shape)
     own = SheetWriter(directory) if writer is None else None
     root = os.path.abspath(str(directory))
     os.makedirs(root, exist_ok=True)
@@ -393,7 +404,7 @@ def interpolation_frames(generator_or_checkpoint, directory: str, anchors: Union
             z = latents[first:first + batch_size]
             count = z.shape[0]
             if count < batch_size:
-                z = torch.cat([z, z[-1:].expand(batch_size - count, -1)], dim=0)
+                z = torch.cat([z, z[-1:].expand(batch_size - count, *z.shape[1:])], dim=0)
             sheets = sample_sheets(sampler(z.contiguous()))
             B, C, H, TW, _ = sheets.shape
             names = [os.path.join(root, f"frame_{first + b:05d}.png") for b in range(count)]

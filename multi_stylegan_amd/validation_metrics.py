@@ -27,6 +27,7 @@ import torch.distributed as torch_dist
 import torch.nn as nn
 
 from . import _lib, misc
+from .ssim import ms_ssim
 
 
 def _ranks() -> int:
@@ -38,7 +39,7 @@ def _ranks() -> int:
 __all__ = ["IS", "FID", "FVD", "FeatureMoments", "frechet_distance", "frechet_distance_from_moments", "inception_score",
            "metric_inputs", "select_frames", "KID", "KVD", "PrecisionRecall", "PrecisionRecallVideo", "FeatureRows",
            "ManifoldScores", "kernel_distance", "manifold_scores", "subset_indices", "SWD", "SWVD", "laplacian_pyramid",
-           "swd_positions", "swd_descriptors", "swd_directions", "sliced_wasserstein"]
+           "swd_positions", "swd_descriptors", "swd_directions", "sliced_wasserstein", "MSSSIM", "MSSSIMVideo", "DiversityScore"]
 
 
 def select_frames(images: torch.Tensor, channel: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -1013,6 +1014,106 @@ class SWD(_SlicedWasserstein):
 class SWVD(_SlicedWasserstein):
     """Sliced Wasserstein video distance: the whole clip of channel ``c`` (as ``FVD`` takes it); the ``T`` frames are the
     planes of a patch, so a descriptor spans time."""
+
+    def _inputs(self, images, channel):
+        return metric_inputs(images, channel, t=None, size=None, normalize=None, planes=1)
+
+
+# ------------------------------------------------------------------------------------------------------ MS-SSIM diversity
+# MSSSIM / MSSSIMVideo (DESIGN.md section 5, "MS-SSIM"; Odena et al. 2017, section 4.3): the mean pairwise multi-scale structural
+# similarity INSIDE a set, for the generated samples beside the dataset's.  Generated far above real: the generator repeats
+# itself.  No feature network; on the GPU every pair is two planes through csrc/ssim.hip (ssim.py: ms_ssim).
+class DiversityScore(NamedTuple):
+    fake: float
+    real: float
+    gap: float
+
+
+class _MsSsimDiversity(_Metric):
+    """Per channel the samples of both kinds are kept on ``device`` as ``[n, P, H, W]`` fp32 planes at their own size (1000
+    frames of 256 x 256: 262 MB per channel and set; ``MSSSIMVideo`` times ``T``); every rank contributes ``share =
+    ceil(data_samples / ranks)`` samples of each kind.  A permutation drawn from ``seed`` forms the disjoint pairs ``(pi(2 i),
+    pi(2 i + 1))`` of a rank's samples, at most ``pairs`` of them; the score of a set is the mean ``ms_ssim`` over the pairs of
+    all ranks (the sum and the count are all-reduced).  The dataset's score is cached across calls.  Frames are expected in
+    ``[0, data_range]``.  The score per channel is ``DiversityScore(fake, real, gap = fake - real)``."""
+
+    def __init__(self, device: Union[str, torch.device] = "cuda", data_parallel: bool = False, batch_size: int = 1,
+                 data_samples: int = 1000, no_rfp: bool = False, no_gfp: bool = False, pairs: Optional[int] = None,
+                 seed: int = 0, data_range: float = 1.0) -> None:
+        self.network = None
+        self.device, self.batch_size, self.data_samples = device, batch_size, data_samples
+        self.no_rfp, self.no_gfp = no_rfp, no_gfp
+        self.pairs, self.seed, self.data_range = pairs, int(seed), float(data_range)
+        self.real = None                                # (scores per channel, samples kept), cached across calls
+
+    def _inputs(self, images: torch.Tensor, channel: int) -> torch.Tensor:
+        raise NotImplementedError
+
+    def _planes(self, images: torch.Tensor, channel: int) -> torch.Tensor:
+        return self._inputs(images, channel)[:, 0].float()                     # [B, T', H, W]: the frames are the planes
+
+    def _pair_mean(self, planes: torch.Tensor) -> float:
+        n = planes.shape[0]
+        k = n // 2 if self.pairs is None else min(n // 2, int(self.pairs))
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(self.seed)).to(planes.device)
+        total = torch.zeros((), dtype=torch.float64, device=planes.device)
+        chunk = max(int(self.batch_size), 64)
+        for i in range(0, k, chunk):
+            j = min(i + chunk, k)
+            total += ms_ssim(planes[perm[2 * i:2 * j:2]], planes[perm[2 * i + 1:2 * j:2]], data_range=self.data_range).double().sum()
+        stats = torch.stack([total, torch.tensor(float(k), dtype=torch.float64, device=planes.device)])
+        if _ranks() > 1:
+            torch_dist.all_reduce(stats)
+        if float(stats[1]) < 1:
+            raise ValueError(f"{type(self).__name__}: {n} samples form no pair")
+        return float(stats[0] / stats[1])
+
+    @torch.no_grad()
+    def __call__(self, generator: nn.Module, dataset: Iterable):
+        channels = self._channels()
+        share = math.ceil(self.data_samples / _ranks())
+        if self.real is None:
+            real = [[] for _ in channels]
+            held = 0
+            for real_images in dataset:
+                real_images = real_images.to(self.device)
+                for k, c in enumerate(channels):
+                    real[k].append(self._planes(real_images, c))
+                held += real_images.shape[0]
+                if held >= share:
+                    break
+            if held == 0:
+                raise ValueError("the dataset is empty")
+            if held < share:
+                warnings.warn(f"{type(self).__name__}: the dataset held {held} samples, fewer than data_samples = "
+                              f"{self.data_samples}; the real score (cached from now on) is that of {held} samples")
+            kept = min(held, share)
+            self.real = ([self._pair_mean(torch.cat(r)[:kept]) for r in real], kept)
+        real_scores, kept = self.real
+        generator.to(self.device).eval()
+        fake = [[] for _ in channels]
+        for _ in range(math.ceil(kept / self.batch_size)):
+            fake_images = generator(input=self._latents(generator))
+            for k, c in enumerate(channels):
+                fake[k].append(self._planes(fake_images, c))
+        scores = []
+        for r, f in zip(real_scores, fake):
+            value = self._pair_mean(torch.cat(f)[:kept])
+            scores.append(DiversityScore(value, r, value - r))
+        return self._result(scores)
+
+
+class MSSSIM(_MsSsimDiversity):
+    """Mean pairwise MS-SSIM of generated frames beside that of dataset frames: channel ``c`` of one drawn time step (as ``FID``
+    draws it) at its own size, ``metric_inputs(..., size=None, normalize=None, planes=1)``."""
+
+    def _inputs(self, images, channel):
+        return metric_inputs(images, channel, t=_draw_time_step(images), size=None, normalize=None, planes=1)
+
+
+class MSSSIMVideo(_MsSsimDiversity):
+    """The same over whole clips of channel ``c`` (as ``FVD`` takes them): the ``T`` frames are the planes of a sample, and a
+    pair scores the mean over them."""
 
     def _inputs(self, images, channel):
         return metric_inputs(images, channel, t=None, size=None, normalize=None, planes=1)

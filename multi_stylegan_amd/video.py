@@ -458,26 +458,35 @@ class MjpegWriter:
 @torch.no_grad()
 def interpolation_video(generator_or_checkpoint, path: str, anchors: Union[int, torch.Tensor] = 16, steps_per_anchor: int = 100,
                         batch_size: int = 32, seed: Optional[int] = None, use_graph: bool = True, fps: float = 60,
-                        quality: int = 90) -> int:
+                        quality: int = 90, anchors_are_latents: bool = False) -> int:
     """scripts/gan_latent_space_interpolation.py:28-59 with its video as the output: the frames ``interpolation_frames`` writes
     as ``frame_{index:05d}.png`` -- the same latents, batches and padding rule, the same
     ``sample_sheets(...).reshape(B, C * H, T * W, 3)`` pictures -- as the frames of one Motion-JPEG AVI at ``path``.  Returns
-    their number."""
+    their number.  ``anchors_are_latents=True``: ``[K, D]`` or ``[K, n, D]`` W / W+ anchors, as there."""
     from .inference import GeneratorSampler
     device = _device_of(generator_or_checkpoint)
     generator = _generator_of(generator_or_checkpoint, device)
+    latent_shape = None
+    if anchors_are_latents:
+        if not isinstance(anchors, torch.Tensor) or anchors.ndim not in (2, 3):
+            raise ValueError("anchors_are_latents=True takes [K, D] or [K, n, D] W / W+ anchors")
+        latent_shape = tuple(anchors.shape[1:])
+        anchors = anchors.reshape(anchors.shape[0], -1)
     if not isinstance(anchors, torch.Tensor):
         draw = None if seed is None else torch.Generator().manual_seed(int(seed))
         anchors = torch.randn(int(anchors), generator.latent_dimensions, generator=draw)
     latents = interpolation_latents(anchors.to(device=device, dtype=torch.float32), steps_per_anchor)
     total = latents.shape[0]
-    sampler = GeneratorSampler(generator, batch_size=batch_size, randomize_noise=False, use_graph=use_graph, device=device)
+    if latent_shape is not None:
+        latents = latents.reshape(total, *latent_shape)
+    sampler = GeneratorSampler(generator, batch_size=batch_size, randomize_noise=False, use_graph=use_graph, device=device,
+                               latent_shape=latent_shape)
     with MjpegWriter(path, fps=fps, quality=quality) as video:
         for first in range(0, total, batch_size):
             z = latents[first:first + batch_size]
             count = z.shape[0]
             if count < batch_size:
-                z = torch.cat([z, z[-1:].expand(batch_size - count, -1)], dim=0)
+                z = torch.cat([z, z[-1:].expand(batch_size - count, *z.shape[1:])], dim=0)
             sheets = sample_sheets(sampler(z.contiguous()))
             B, C, H, TW, _ = sheets.shape
             video.submit(sheets.reshape(B, C * H, TW, 3)[:count])
