@@ -4,7 +4,10 @@ selects the kernel it names and that the table as a whole reaches every large-ti
 tests/test_hip_conv.py runs the cases against float64 and asserts the kernel-clock label of what ran.
 
 The shapes sit at or just above each kernel's own floor -- 224 workgroups for the 256 x 256 tiles, 448 for the 128 x 128 row-sharing
-tile, 1024 GEMM rows -- so that the float64 reference stays quick.  They are not the workload's shapes."""
+tile, 1024 GEMM rows -- so that the float64 reference stays quick.  They are not the workload's shapes.
+
+THIN_CASES, UPCONV_CASES and STREAM_GUARD_CASES further down do the same for the two streaming files that come first in the
+selection order, conv_thin.hip and conv_upconv.hip."""
 from collections import namedtuple
 
 Case = namedtuple("Case", "name kind B I O H W k stride pad per_sample fwd dgrad")
@@ -104,3 +107,93 @@ def launches(c, bf16, has_bias=0, epilogue=0):
 def gemm_rows(args):
     """GEMM rows of one grid.z slice of a launch: the pixels of one sample with per-sample weights, of the batch otherwise."""
     return args[OH] * args[OW] * (1 if args[W_BATCH_STRIDE] else args[B_])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The two streaming files that come first in conv_fprop_select: conv_thin.hip (thin N: <= 8 outputs, thin K: <= 8 inputs, and
+# thin K with scalar loads) and conv_upconv.hip.  tests/test_host.py asserts that every row selects THIN / UPCONV and that the
+# tables reach every instantiation and loop edge named below; tests/test_hip_conv.py runs them exactly (small-integer operands)
+# and against float64.
+#
+# cx: the channel count of the map x is a channel slice of (None: x is its own map, I rounded up to 8)
+Thin = namedtuple("Thin", "name B I O H W per_sample cx", defaults=(None,))
+
+THIN_CASES = [
+    # ---- thin N (conv_thin_n_kernel<KC>, KC = Ck / 32; a wave takes groups_per_wave groups of 16 pixels)
+    Thin("n_kc2_floor", 1, 64, 3, 64, 64, False),                # M = 4096, the floor; KC 2
+    Thin("n_one_pixel_group", 1, 64, 5, 17, 241, False),         # M = 4097: the last group holds one pixel; N = 5
+    Thin("n_n1_ragged", 1, 128, 1, 67, 62, False),               # N = 1, M % 16 = 10; KC 4
+    Thin("n_n4_ragged", 1, 128, 4, 67, 62, False),               # N = 4: the second half-wave still carries no real output
+    Thin("n_kc6_per_sample", 2, 192, 4, 50, 47, True),           # KC 6, per-sample, M % 16 = 14
+    Thin("n_n8", 1, 256, 8, 65, 64, False),                      # N = 8, every weight row live; KC 8
+    Thin("n_kc12", 1, 384, 6, 67, 62, False),                    # KC 12
+    Thin("n_kc16_per_sample", 2, 512, 6, 47, 45, True),          # KC 16, the RGB heads, per-sample, M % 16 = 3
+    Thin("n_two_groups", 1, 64, 3, 363, 362, False),             # M = 131406: groups_per_wave 2; 8213 groups: the last wave takes one of its two and breaks
+    Thin("n_two_groups_per_sample", 3, 64, 5, 210, 209, True),   # groups_per_wave 2 through the sample count (2744 groups x 3)
+    Thin("n_eight_groups", 1, 64, 3, 1025, 1024, False),         # groups_per_wave clamped at 8 (65600 groups); 134 MB of input
+    Thin("n_channel_slice", 1, 64, 3, 64, 64, False, 72),        # Cx = 72 > Ck = 64: the first 64 channels of a 72-channel map
+    # ---- thin K (conv_thin_k_kernel<NV, 8> and, for N = 512 on whole 64-byte runs, conv_thin_k_sload_kernel<64>; NV = N / 8)
+    Thin("k_nv8_floor", 1, 6, 64, 64, 64, False),                # NV 8, the floor
+    Thin("k_nv16_one_channel", 1, 1, 128, 17, 241, False),       # NV 16, one real input channel, M % 4 = 1
+    Thin("k_nv32", 2, 6, 256, 47, 45, False),                    # NV 32
+    Thin("k_nv32_per_sample", 2, 8, 256, 64, 64, True),          # NV 32, per-sample, all eight inputs real
+    Thin("k_sload_one_group", 1, 6, 512, 17, 241, False),        # scalar-load kernel; M = 4097, 8 groups per wave: the last wave holds one group
+    Thin("k_nv64_per_sample", 3, 6, 512, 67, 61, True),          # 4087 pixels per sample: the stride fails the 64-byte test, NV 64 on the plain kernel
+    Thin("k_sixteen_groups", 1, 6, 512, 363, 362, False),        # groups_per_wave 16; the last wave holds 14.  134 MB of output
+]
+THIN_BY_NAME = {c.name: c for c in THIN_CASES}
+THIN_LARGE = ("n_eight_groups", "k_sixteen_groups")              # rows above 100 MB: operands and reference on the device
+THIN_K_RESIDUAL_CASES = ("k_nv8_floor", "k_nv32_per_sample", "k_sload_one_group", "k_nv64_per_sample")    # the residual-merge legs
+# the layers whose forward AND data gradient are thin launches: (B, I, O, H, W, per_sample)
+THIN_DGRAD_LAYERS = [(2, 512, 6, 47, 45, True), (1, 128, 1, 67, 62, False), (1, 6, 128, 67, 62, False), (1, 256, 8, 65, 64, False)]
+
+# up-convolution (conv_upconv_kernel): I = 512, per-sample weights, N = 4 * O columns in slices of 64 over 8 waves
+Upconv = namedtuple("Upconv", "name B O H W")
+UPCONV_CASES = [
+    Upconv("up_4_slices", 2, 64, 128, 128),                      # 4 slices for 8 waves; each slice is a different sub-pixel (dy, dx)
+    Upconv("up_12_slices", 2, 192, 128, 128),                    # 12 slices: a ragged second round, three slices per sub-pixel
+    Upconv("up_xcd_samples", 16, 64, 128, 128),                  # samples dealt to XCDs with j in {0, 1}
+    Upconv("up_ragged_odd_w", 2, 64, 130, 127),                  # last tile has 126 live rows; odd W in the pixel-shuffle address
+    Upconv("up_one_sample", 1, 64, 256, 128),                    # one sample, 256 tiles
+]
+
+# one step outside a rule: another kernel's name.  Asserted on the host only.  (family, row, the kernel that takes it)
+STREAM_GUARD_CASES = [
+    ("thin", Thin("guard_n_below_floor", 1, 64, 3, 63, 65, False), "REG"),          # M = 4095
+    ("thin", Thin("guard_k_below_floor", 1, 6, 64, 63, 65, False), "REG"),          # M = 4095
+    ("thin", Thin("guard_k_nv24", 2, 6, 192, 50, 47, True), "REG"),                 # N / 8 = 24 does not divide 64
+    ("upconv", Upconv("guard_up_128_tiles", 1, 64, 128, 128), "DMA"),               # 128 tiles, below the 256 needed
+    ("upconv", Upconv("guard_up_16383_pixels", 3, 128, 129, 127), "PP"),            # one pixel below the 16384 of the rule
+    ("upconv", Upconv("guard_up_o96", 2, 96, 128, 128), "DMA"),                     # O not a multiple of 64
+]
+
+UPCONV_I = 512
+
+
+def thin_launch(c, bf16, has_bias=0, epilogue=0):
+    """msg_conv2d_fprop_launch_plan arguments of a Thin row as the Python layer forms them: Cx = the map's channels in whole 16-byte
+    vectors, Ck = I rounded up to a 128-byte run, ldy = O rounded up to 8, the per-sample weight stride one dense image."""
+    ck = _up(c.I, 64)
+    return (bf16, c.B, c.H, c.W, c.cx or _up(c.I, 8), ck, c.H, c.W, c.O, _up(c.O, 8), 1, 1, 1, 0, 1, 0, int(c.per_sample) * c.O * ck,
+            has_bias, epilogue)
+
+
+def upconv_launch(c, bf16):
+    """... of an Upconv row: a 1x1 conv to the 4 * O sub-pixel planes, stored pixel-shuffled, one dense weight image per sample."""
+    return (bf16, c.B, c.H, c.W, UPCONV_I, UPCONV_I, c.H, c.W, 4 * c.O, _up(c.O, 8), 1, 1, 1, 0, 1, 1, 4 * c.O * UPCONV_I, 0, 0)
+
+
+def thin_groups_per_wave(args):
+    """The pixel groups each wave of a thin launch takes.  The plan query does not show it, so this MIRRORS thin_grid in
+    csrc/conv_thin.hip and must move with it: thin N (N <= 8) has groups of 16 pixels, one group per 8192 groups of the launch,
+    between 1 and 8; thin K has groups of 64 / (N / 8) pixels, one per 16384, rounded up to whole steps of THIN_K_U = 8, between 8
+    and 32."""
+    thin_n = args[N_] <= 8
+    ppw = 16 if thin_n else 64 // (args[N_] // 8)
+    groups = (gemm_rows(args) + ppw - 1) // ppw
+    samples = args[B_] if args[W_BATCH_STRIDE] else 1
+    per, lo, hi = (8192, 1, 8) if thin_n else (16384, 8, 32)
+    g = (groups * samples + per - 1) // per
+    if not thin_n:
+        g = _up(g, 8)
+    return min(max(g, lo), hi)

@@ -10,7 +10,8 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
-from conv_kernel_cases import BY_NAME, CASES as LARGE_TILE_CASES, EPILOGUE_CASES
+from conv_kernel_cases import (BY_NAME, CASES as LARGE_TILE_CASES, EPILOGUE_CASES, THIN_BY_NAME, THIN_CASES, THIN_DGRAD_LAYERS,
+                               THIN_K_RESIDUAL_CASES, THIN_LARGE, UPCONV_CASES, UPCONV_I)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -1151,6 +1152,247 @@ def test_thin_pointwise_conv_kernels(case):
     if o % 8:                                                             # the padded channel-vector behind the real outputs
         base = y._base if y._base is not None else y
         assert base.shape[-1] == 8 * ((o + 7) // 8) or base.shape[1] == 8 * ((o + 7) // 8)
+
+
+# ---- conv_thin.hip and conv_upconv.hip at every loop edge (tests/conv_kernel_cases.py: THIN_CASES, UPCONV_CASES), two passes each:
+#   exact -- small-integer operands: every product and partial sum is an integer below 2^24, exact in fp32 in any order, and the
+#            result is asserted representable in bf16, so the kernel's output must EQUAL the float64 reference;
+#   float -- bf16-rounded normals (scaled as _large_tile_operands), each element within
+#                |got - ref| <= 2^-8 |ref| + K 2^-23 S,      S = the same contraction of |x|, |w| (+ |bias|) in float64:
+#            one round-to-nearest-even bf16 store (f2bf: at most 2^-8 / (1 + 2^-8) of the fp32 value, whose own error the second
+#            term's factor two absorbs) and K fp32 roundings of 2^-24 S in any order, doubled.  Derived, not measured.
+_CPU_REFERENCE_MACS = 1e9           # float64 contractions up to this size run on the CPU (under two seconds), larger ones on the device
+
+
+def _stream_rng(name):
+    return torch.Generator(device=DEV).manual_seed(sum(ord(ch) for ch in name))
+
+
+def _stream_values(g, shape, k, exact, weight=False):
+    """fp32 device tensor of bf16-exact values for a contraction of length k.  exact: integers -- {-2..2} for k <= 8; for k >= 64
+    activations in {-1, 0, 1} and weights in {-1, 0, 1} with one entry in eight non-zero.  Else normals, weights scaled by 1 / sqrt k."""
+    if not exact:
+        v = torch.randn(shape, generator=g, device=DEV)
+        return (v / math.sqrt(k) if weight else v).bfloat16().float()
+    if k <= 8:
+        return torch.randint(-2, 3, shape, generator=g, device=DEV).float()
+    assert k >= 64
+    if not weight:
+        return torch.randint(-1, 2, shape, generator=g, device=DEV).float()
+    sign = torch.randint(0, 2, shape, generator=g, device=DEV).float() * 2 - 1
+    return sign * (torch.rand(shape, generator=g, device=DEV) < 0.125)
+
+
+def _stream_bias(g, o, exact):
+    return torch.randint(-4, 5, (o,), generator=g, device=DEV).float() if exact else torch.randn(o, generator=g, device=DEV)
+
+
+def _pointwise_reference(xn, w, bias, dev):
+    """A 1x1 conv by its definition, a float64 matrix product per pixel: xn [B, H, W, I], w [(B,) O, I], bias [O] | None -> (y, S)
+    [B, H, W, O] on `dev`, S the same contraction of the absolute values."""
+    x64 = xn.to(dev, torch.float64).flatten(1, 2)
+    w64 = w.to(dev, torch.float64).reshape(-1, *w.shape[-2:]).transpose(1, 2)            # [B or 1, I, O]
+    b64 = torch.zeros((), dtype=torch.float64, device=dev) if bias is None else bias.to(dev, torch.float64)
+    shape = (*xn.shape[:3], w.shape[-2])
+    return (x64 @ w64 + b64).view(shape), (x64.abs() @ w64.abs() + b64.abs()).view(shape)
+
+
+def _upconv_reference(xn, w, dev):
+    """The 2x2 stride-2 transposed conv by its definition, y[b, 2h + dy, 2w + dx, c] = sum_k x[b, h, w, k] w[b, c, k, dy, dx], as a
+    float64 matrix product per pixel to the four sub-pixel planes: xn [B, H, W, I], w [B, O, I, 2, 2] -> (y, S) [B, 2H, 2W, O]."""
+    b, h, w_, i = xn.shape
+    o = w.shape[1]
+    x64 = xn.to(dev, torch.float64).flatten(1, 2)
+    w64 = w.to(dev, torch.float64).permute(0, 2, 3, 4, 1).reshape(b, i, 4 * o)           # column (2 dy + dx) * O + c
+    shuffle = lambda p: p.view(b, h, w_, 2, 2, o).permute(0, 1, 3, 2, 4, 5).reshape(b, 2 * h, 2 * w_, o)
+    return shuffle(x64 @ w64), shuffle(x64.abs() @ w64.abs())
+
+
+def _nhwc(y, dev):
+    """The [B, H, W, C] view of a kernel's result, on the reference's device."""
+    return y.detach().permute(0, 2, 3, 1).to(dev)
+
+
+def _worst_nhwc(got, ref):
+    diff = (got.double() - ref).abs()
+    at = tuple(int(v) for v in np.unravel_index(int(diff.argmax()), diff.shape))
+    return {"worst (sample, row, column, channel)": at, "got": float(got[at]), "want": float(ref[at]), "wrong elements": int((diff > 0).sum())}
+
+
+def _assert_exact(y, ref, what):
+    """The exact pass: the reference itself must be representable in bf16 -- a condition on the operands -- and the kernel's
+    output must then equal it."""
+    want = ref.bfloat16()
+    assert torch.equal(want.double(), ref), (what, "the reference is not representable in bf16", float(ref.abs().max()))
+    got = _nhwc(y, ref.device)
+    assert got.shape == want.shape and got.dtype == torch.bfloat16, (what, got.shape, want.shape)
+    assert torch.equal(got, want), (what, _worst_nhwc(got, ref))
+
+
+def _assert_within_bound(y, ref, bound, what):
+    """The float pass: every element within its own derived bound.  -> the worst error / bound ratio."""
+    got = _nhwc(y, ref.device)
+    assert got.shape == ref.shape and got.dtype == torch.bfloat16, (what, got.shape, ref.shape)
+    err = (got.double() - ref).abs()
+    ratio = float(torch.where(err > 0, err / bound, torch.zeros_like(err)).max())
+    print(f"\n{what}: worst error / bound {ratio:.3f}")
+    assert bool((err <= bound).all()), (what, ratio, _worst_nhwc(got, ref))
+    return ratio
+
+
+def _thin_input(xn, cx=None):
+    """xn [B, H, W, I] fp32 -> the bf16 map in the compute layout; cx: as the first I channels of a cx-channel map whose other
+    channels hold NaN."""
+    if cx is None:
+        return xn.permute(0, 3, 1, 2), None
+    wide = torch.full((*xn.shape[:3], cx), float("nan"), dtype=torch.bfloat16, device=DEV)
+    wide[..., :xn.shape[3]] = xn
+    return wide.permute(0, 3, 1, 2)[:, :xn.shape[3]], wide
+
+
+def _padded_vector(y, channels):
+    """All `channels` stored channels of a result whose channel vector is padded, [B, channels, H, W]."""
+    from multi_stylegan_amd import conv_ops
+    yv, cx = conv_ops._nhwc_view(y.detach())
+    assert yv.data_ptr() == y.data_ptr() and cx == channels, (cx, channels)
+    return yv.as_strided((y.shape[0], channels, *y.shape[2:]), yv.stride(), yv.storage_offset())
+
+
+@pytest.mark.parametrize("case", THIN_CASES, ids=[c.name for c in THIN_CASES])
+def test_thin_kernels_exact_and_against_float64(case):
+    """Every row of THIN_CASES -- each instantiation of conv_thin_n_kernel (KC 2 .. 16), conv_thin_k_kernel (NV 8 .. 64) and
+    conv_thin_k_sload_kernel, one, two and eight (thin N) or eight and sixteen (thin K) groups per wave with the last wave cut
+    short, last groups of one pixel, N either side of the half-wave boundary, shared and per-sample weights, an input that is a
+    channel slice of a wider map full of NaN -- plain and with a bias, under the THIN clock label: the exact pass (integer
+    operands, output == float64 reference) and the float pass (per-element bound, see above).  Thin N: channels N..7 of the stored
+    8-wide vector are exactly zero.  Largest error / bound of the float pass, measured: 0.996
+    (k_nv8_floor and the other thin K rows; thin N 0.991, n_two_groups with a bias) -- the store term alone, which is tight where
+    a value sits just above a power of two."""
+    from multi_stylegan_amd import conv_ops
+    c = case
+    dev = DEV if c.name in THIN_LARGE or c.B * c.H * c.W * c.I * c.O > _CPU_REFERENCE_MACS else "cpu"
+    g = _stream_rng(c.name)
+    geo = conv_ops.Geometry("conv", 1, 1, 1, 0, (c.H, c.W), c.per_sample)
+    for exact in (True, False):
+        xn = _stream_values(g, (c.B, c.H, c.W, c.I), c.I, exact)
+        w = _stream_values(g, ((c.B,) if c.per_sample else ()) + (c.O, c.I), c.I, exact, weight=True)
+        xs, wide = _thin_input(xn, c.cx)
+        x = xs if wide is not None else conv_ops.to_compute_layout(xs, torch.bfloat16)
+        for bias in (None, _stream_bias(g, c.O, exact)):
+            what = f"{c.name} {'exact' if exact else 'float'}{' bias' if bias is not None else ''}"
+            ref, s = _pointwise_reference(xn, w, bias, dev)
+            y = _clocked(lambda: conv_ops._f_raw(x, w[..., None, None], bias, geo), "THIN")
+            assert y.shape == (c.B, c.O, c.H, c.W)
+            if exact:
+                _assert_exact(y, ref, what)
+            else:
+                _assert_within_bound(y, ref, 2.0 ** -8 * ref.abs() + c.I * 2.0 ** -23 * s, what)
+            if c.O < 8:
+                assert not bool(_padded_vector(y, 8)[:, c.O:].ne(0).any()), (what, "pad channels of the 8-wide vector")
+            if wide is not None:
+                assert bool(torch.isfinite(y).all()), (what, "read beyond the slice")
+
+
+@pytest.mark.parametrize("name", THIN_K_RESIDUAL_CASES)
+def test_thin_k_residual_merge_exact_and_against_float64(name):
+    """The residual epilogue of the thin K kernels, y = (bf16(conv) + map) * gain, at NV 8 shared, NV 32 per-sample (res_bstride),
+    NV 64 on the scalar-load kernel and NV 64 per-sample on the plain kernel, under the THIN clock label, against the float64
+    form (bf16(conv64) + map) * gain: exact with gain 0.5, and within the float bound plus 2^-8 gain |conv| for the rounding
+    of the conv (gain 1 / sqrt 2).  Three legs: dense operands; the output written through out= into a channel slice of a wider map
+    (ldy > N) pre-filled with NaN, whose other channels must still be NaN; the map read from such a slice (res_ld > N).
+    Largest error / bound of the float pass, measured: 0.992 (k_nv64_per_sample, the same in all three legs)."""
+    from multi_stylegan_amd import conv_ops
+    c = THIN_BY_NAME[name]
+    g = _stream_rng(c.name + " residual")
+    geo = conv_ops.Geometry("conv", 1, 1, 1, 0, (c.H, c.W), c.per_sample)
+    off, width = 8, c.O + 24                           # the slice [8, 8 + N) of a map of N + 24 channels
+
+    def in_slice(values=None):
+        wide = torch.full((c.B, c.H, c.W, width), float("nan"), dtype=torch.bfloat16, device=DEV)
+        if values is not None:
+            wide[..., off:off + c.O] = values
+        return wide, wide.permute(0, 3, 1, 2)[:, off:off + c.O]
+
+    for exact in (True, False):
+        gain = 0.5 if exact else 1 / math.sqrt(2)
+        xn = _stream_values(g, (c.B, c.H, c.W, c.I), c.I, exact)
+        w = _stream_values(g, ((c.B,) if c.per_sample else ()) + (c.O, c.I), c.I, exact, weight=True)
+        # the map: integers in {-4..4} or normals, the values a bias takes
+        rn = _stream_bias(g, c.B * c.H * c.W * c.O, exact).view(c.B, c.H, c.W, c.O).bfloat16()
+        x = conv_ops.to_compute_layout(xn.permute(0, 3, 1, 2), torch.bfloat16)
+        conv, s = _pointwise_reference(xn, w, None, "cpu")
+        ref = (conv.bfloat16().double() + rn.cpu().double()) * gain
+        bound = 2.0 ** -8 * ref.abs() + 2.0 ** -8 * gain * conv.abs() + c.I * 2.0 ** -23 * (s + rn.cpu().double().abs()) * gain
+        res = rn.permute(0, 3, 1, 2)
+        for leg in ("dense", "out slice", "residual slice"):
+            what = f"{c.name} residual {'exact' if exact else 'float'} {leg}"
+            wide_out, out = in_slice() if leg == "out slice" else (None, None)
+            rmap = in_slice(rn)[1] if leg == "residual slice" else res
+            y = _clocked(lambda: conv_ops._f_raw(x, w[..., None, None], None, geo, residual=(rmap, gain), out=out), "THIN")
+            if out is not None:
+                assert y.data_ptr() == out.data_ptr() and y.stride() == out.stride(), what
+                outside = torch.cat([wide_out[..., :off], wide_out[..., off + c.O:]], dim=-1)
+                assert bool(torch.isnan(outside).all()), (what, "stored outside the slice")
+            if exact:
+                _assert_exact(y, ref, what)
+            else:
+                _assert_within_bound(y, ref, bound, what)
+
+
+@pytest.mark.parametrize("layer", THIN_DGRAD_LAYERS, ids=["512to6_per_sample", "128to1", "6to128", "256to8"])
+def test_thin_kernels_as_data_gradients(layer):
+    """Four layers whose forward and data gradient are BOTH thin launches (thin N one way, thin K the other), through
+    conv_ops._ConvF and torch.autograd.grad, both launches under the THIN clock label: exact pass and float pass against the
+    float64 products y = x w^T and gx = gy w.  The weights serve both contractions: they follow the forward's operand rule, the
+    incoming gradient follows the rule for the data gradient's K = O.  Largest error / bound of the float pass, measured: 0.996
+    (the thin K launch of each layer; thin N 0.967)."""
+    from multi_stylegan_amd import conv_ops
+    b, i, o, h, w_, per_sample = layer
+    g = _stream_rng(f"dgrad {layer}")
+    geo = conv_ops.Geometry("conv", 1, 1, 1, 0, (h, w_), per_sample)
+    for exact in (True, False):
+        xn = _stream_values(g, (b, h, w_, i), i, exact)
+        w = _stream_values(g, ((b,) if per_sample else ()) + (o, i), i, exact, weight=True)
+        gyn = _stream_values(g, (b, h, w_, o), o, exact)
+        yr, ys = _pointwise_reference(xn, w, None, "cpu")
+        gxr, gxs = _pointwise_reference(gyn, w.transpose(-1, -2), None, "cpu")
+        xd = conv_ops.to_compute_layout(xn.permute(0, 3, 1, 2), torch.bfloat16).detach().requires_grad_(True)
+        gyd = conv_ops.to_compute_layout(gyn.permute(0, 3, 1, 2), torch.bfloat16)
+        y = _clocked(lambda: conv_ops._ConvF.apply(xd, w[..., None, None], None, geo), "THIN")
+        gx, = _clocked(lambda: torch.autograd.grad(y, xd, gyd), "THIN")
+        assert y.shape == (b, o, h, w_) and gx.shape == (b, i, h, w_)
+        for name, got, ref, s, k in (("forward", y, yr, ys, i), ("data gradient", gx, gxr, gxs, o)):
+            what = f"{i} -> {o} {'exact' if exact else 'float'} {name}"
+            if exact:
+                _assert_exact(got, ref, what)
+            else:
+                _assert_within_bound(got, ref, 2.0 ** -8 * ref.abs() + k * 2.0 ** -23 * s, what)
+
+
+@pytest.mark.parametrize("case", UPCONV_CASES, ids=[c.name for c in UPCONV_CASES])
+def test_upconv_kernel_exact_and_against_float64(case):
+    """Every row of UPCONV_CASES -- O = 64 (four slices for eight waves, each another sub-pixel), O = 192 (a ragged second round of
+    slices), sixteen samples dealt to the XCDs in two rounds, a ragged last tile on a map of odd width, one sample -- under the
+    UPCONV clock label, two launches bit-identical: the exact pass (integer operands, output == the float64 transposed
+    convolution) and the float pass (per-element bound, K = 512).  Largest error / bound of the float pass, measured: 0.942
+    (up_xcd_samples)."""
+    from multi_stylegan_amd import conv_ops
+    c, i = case, UPCONV_I
+    g = _stream_rng(c.name)
+    geo = conv_ops.Geometry("up2", 2, 2, 1, 0, (c.H, c.W), True)
+    for exact in (True, False):
+        what = f"{c.name} {'exact' if exact else 'float'}"
+        xn = _stream_values(g, (c.B, c.H, c.W, i), i, exact)
+        w = _stream_values(g, (c.B, c.O, i, 2, 2), i, exact, weight=True)
+        x = conv_ops.to_compute_layout(xn.permute(0, 3, 1, 2), torch.bfloat16)
+        ref, s = _upconv_reference(xn, w, DEV)         # (4e9 multiply-adds and more: float64 on the device)
+        y = _clocked(lambda: conv_ops._f_raw(x, w, None, geo), "UPCONV")
+        assert y.shape == (c.B, c.O, 2 * c.H, 2 * c.W)
+        assert torch.equal(y, _clocked(lambda: conv_ops._f_raw(x, w, None, geo), "UPCONV")), (what, "two launches differ")
+        if exact:
+            _assert_exact(y, ref, what)
+        else:
+            _assert_within_bound(y, ref, 2.0 ** -8 * ref.abs() + i * 2.0 ** -23 * s, what)
 
 
 @pytest.mark.parametrize("shape", [(3, 6, 40, 64), (2, 6, 5, 32), (1, 3, 33, 96), (2, 7, 16, 128), (2, 6, 12, 20)])

@@ -1181,3 +1181,68 @@ def test_conv_kernel_case_table_selects_the_kernels_it_names():
     assert any(a[T.CX] < a[T.CK] for _, a in pp), "Cx < Ck"
     row_sharing = [a for c, a in fwd if c.fwd != "PP"] + [a for c, a in dgrad if c.dgrad != "PP"]
     assert {32, 64, 128, 256, 512} <= {a[T.OW] for a in row_sharing}
+
+
+def test_streaming_conv_case_tables_select_the_kernels_they_name():
+    """THIN_CASES, UPCONV_CASES and STREAM_GUARD_CASES of tests/conv_kernel_cases.py, the shapes test_hip_conv.py runs on
+    conv_thin.hip and conv_upconv.hip: msg_conv2d_fprop_launch_plan names THIN for every thin row plain and with a bias, and for
+    the thin K rows with the residual epilogue too; UPCONV for every up-convolution row; and for each guard row, one step outside
+    a rule, the other kernel the row names.  Then the tables as a whole: every instantiation of the thin kernels (KC = Ck / 32, NV =
+    N / 8), the output counts either side of the half-wave boundary, both weight modes, ragged pixel counts, every
+    groups_per_wave the grid rule gives (through the table's mirror of thin_grid), and for the up-convolution fewer slices than
+    waves, a ragged round of slices, both workgroup orders and a ragged last tile."""
+    import conv_kernel_cases as table
+    from multi_stylegan_amd import _lib
+    from multi_stylegan_amd.build import build
+    from tools.gen_dispatch_table import fprop_plan
+    build(verbose=False)
+    lib, T, bf16 = _lib.lib(), table, _lib.MSG_BF16
+    code = lambda kernel: getattr(_lib, "MSG_PLAN_" + kernel)
+    names = [c.name for c in T.THIN_CASES + T.UPCONV_CASES] + [c.name for _, c, _ in T.STREAM_GUARD_CASES]
+    assert len(set(names)) == len(names)
+    assert set(T.THIN_LARGE) | set(T.THIN_K_RESIDUAL_CASES) <= set(T.THIN_BY_NAME)
+    thin_n, thin_k = [], []
+    for c in T.THIN_CASES:
+        legs = [(0, 0), (1, 0)] + ([(0, 2)] if c.O > 8 else [])
+        for has_bias, epilogue in legs:
+            assert fprop_plan(lib, list(T.thin_launch(c, bf16, has_bias, epilogue)))[0] == code("THIN"), (c.name, has_bias, epilogue)
+        (thin_n if c.O <= 8 else thin_k).append((c, T.thin_launch(c, bf16)))
+    assert all(a[T.CX] >= a[T.CK] for _, a in thin_n) and all(a[T.CX] == 8 for _, a in thin_k)      # which of the two modes a row is
+    assert all(T.THIN_BY_NAME[n].O > 8 for n in T.THIN_K_RESIDUAL_CASES)
+    for c in T.UPCONV_CASES:
+        assert fprop_plan(lib, list(T.upconv_launch(c, bf16)))[0] == code("UPCONV"), c.name
+    for family, c, kernel in T.STREAM_GUARD_CASES:
+        assert kernel not in ("THIN", "UPCONV")
+        args = T.thin_launch(c, bf16) if family == "thin" else T.upconv_launch(c, bf16)
+        assert fprop_plan(lib, list(args))[0] == code(kernel), (c.name, "guard")
+    # the N = 1 and N = 4 rows differ in N only: one side and the other of the half-wave boundary on the same pixels
+    n1, n4 = T.THIN_BY_NAME["n_n1_ragged"], T.THIN_BY_NAME["n_n4_ragged"]
+    assert n1._replace(name="", O=0) == n4._replace(name="", O=0) and (n1.O, n4.O) == (1, 4)
+    # thin N
+    assert {a[T.CK] // 32 for _, a in thin_n} == {2, 4, 6, 8, 12, 16}, "KC"
+    assert {1, 4, 5, 8} <= {a[T.N_] for _, a in thin_n}, "N"
+    assert {c.per_sample for c, _ in thin_n} == {False, True}
+    assert any(T.gemm_rows(a) % 16 for _, a in thin_n), "ragged last group"
+    assert any(T.gemm_rows(a) % 16 == 1 for _, a in thin_n), "a last group of one pixel"
+    assert any(a[T.CX] > a[T.CK] for _, a in thin_n), "a channel slice of a wider map"
+    assert {T.thin_groups_per_wave(a) for _, a in thin_n} == {1, 2, 8}
+    # thin K
+    assert {a[T.N_] // 8 for _, a in thin_k} == {8, 16, 32, 64}, "NV"
+    assert {c.per_sample for c, _ in thin_k} == {False, True}
+    assert {T.thin_groups_per_wave(a) for _, a in thin_k} == {8, 16}
+    nv64 = [(c, a) for c, a in thin_k if a[T.N_] == 512]
+    # (conv_thin_launch: the scalar-load kernel takes NV 64 when a sample is a whole number of 64-byte runs, 4 pixels)
+    assert any(c.per_sample and c.H * c.W % 4 for c, _ in nv64) and any(not c.per_sample for c, _ in nv64)
+    assert {T.THIN_BY_NAME[n].O // 8 for n in T.THIN_K_RESIDUAL_CASES} == {8, 32, 64}
+    assert sorted(T.THIN_BY_NAME[n].per_sample for n in T.THIN_K_RESIDUAL_CASES if T.THIN_BY_NAME[n].O == 512) == [False, True]
+    # the layers run forward and backward: both launches are thin
+    for b, i, o, h, w, ps in T.THIN_DGRAD_LAYERS:
+        for cin, cout in ((i, o), (o, i)):
+            assert fprop_plan(lib, list(T.thin_launch(T.Thin("", b, cin, cout, h, w, ps), bf16)))[0] == code("THIN"), (b, cin, cout, h, w)
+    # up-convolution
+    up = [T.upconv_launch(c, bf16) for c in T.UPCONV_CASES]
+    assert any(a[T.N_] // 64 < 8 for a in up), "fewer slices than waves"
+    assert any(a[T.N_] // 64 % 8 for a in up if a[T.N_] // 64 > 8), "a ragged round of slices"
+    assert any(a[T.B_] % 8 == 0 and a[T.B_] > 8 for a in up) and any(a[T.B_] % 8 for a in up), "both workgroup orders"
+    assert any(a[T.OH] * a[T.OW] % 128 for a in up), "ragged last tile"
+    assert any(a[T.OW] % 2 for a in up), "odd W"
